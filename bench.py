@@ -13,6 +13,19 @@ accountant construction, aggregate(), compute_budgets(), device execution
 step is a fresh release (fresh nonce).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--records R]
+                       [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line
+(value, ms_per_step, the whole-path roofline figure from the same steps).
+Every release's nonce is a fixed base plus the step's index -- fresh per step,
+the same from run to run -- so with the same arguments the inputs and the
+releases are reproducible.  --dump-outputs DIR writes what the last timed step
+returned (partition_ids.npy, values.npy, float64, in the order the caller
+receives them; above 48 MB a fixed, seeded sample of the rows, whose indices
+are in rows.npy).  Everything else sits behind --full: the CPU baseline (before
+the GPU is touched), the pipelined timing, the per-stage table (`kernels`, one
+more untimed step), the untimed call without the privacy-id range, the PMC
+traffic of profiles/hbm_traffic*.json and, with several ranks, the one-rank
+check below.
        python bench.py --workload config4 [--public]   (BASELINE configs[3]:
        MEAN+VARIANCE, Gaussian, Pareto(1.2) records per privacy id, mpc = 50,
        mcpp = 4, 1e8 partitions; --public: public_partitions = range(1e8))
@@ -22,9 +35,9 @@ options: --dist-backend nccl (RCCL, default; one GPU per rank) or gloo (host-
 staged collectives; ranks may share a GPU: rank r uses GPU r mod #GPUs, which
 is how a one-GPU box rehearses the N-rank path), --exchange auto |
 reduce_scatter | all_to_all (distributed.exchange_partials).  After timing,
-every multi-rank run checks itself (distributed.check_single; --no-check-single
-skips it): each rank keeps the first --check-records of its records (default
-min(records, 1e8, 4e8 / N)), the N ranks release them with a fixed nonce, the
+every multi-rank --full run checks itself (distributed.check_single;
+--no-check-single skips it): each rank keeps the first --check-records of its
+records (default min(records, 1e8, 4e8 / N)), the N ranks release them with a fixed nonce, the
 prefixes are gathered to rank 0, which releases their union as ONE rank with
 the same nonce, and the line reports whether the kept partition sets and the
 exact columns agree (the selected set does not depend on N).
@@ -284,6 +297,29 @@ def _lib_sha() -> str:
         return hashlib.sha256(f.read()).hexdigest()[:16]
 
 
+NONCE0 = 0xBE7C400000000   # release nonce of the run's i-th release: NONCE0 + i
+DUMP_BYTES = 48 << 20      # --dump-outputs writes at most this much
+
+
+def _dump(dirname: str, arrays: dict, suffix: str = "") -> None:
+    """--dump-outputs: device arrays that share their first axis, written as
+    DIR/<name><suffix>.npy in float64.  Above DUMP_BYTES a fixed, seeded
+    sample of the rows is written, with its row indices as rows<suffix>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(8 * (t.numel() // max(n, 1)) for t in arrays.values()) + 8
+    idx = None
+    if n * row_bytes > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(20250202).choice(
+            n, DUMP_BYTES // row_bytes, replace=False))
+        np.save(os.path.join(dirname, f"rows{suffix}.npy"), idx.astype(np.float64))
+    for name, t in arrays.items():
+        if idx is not None:
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"),
+                t.to(torch.float64).cpu().numpy())
+
+
 def _default_workload(args, c4: bool) -> bool:
     """The workload configs[1] / configs[3] (private) name, which the PMC
     passes of tools/gpu_r6_final.sh measure (other inputs: no traffic)."""
@@ -379,7 +415,8 @@ def bench_config5(args):
     if args.gpus != 1:
         raise SystemExit("config5 runs on one GPU (the sweep does not shard)")
     P = args.partitions or 1_000_000
-    cpu = None if args.no_cpu_baseline else _ua_cpu_baseline(1_000_000, P)
+    # --full only: the host restatement of the sweep, before the GPU is touched
+    cpu = _ua_cpu_baseline(1_000_000, P) if args.full and not args.no_cpu_baseline else None
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
     pid, pk, val = generate(args.records, args.pids, P, 0, 1, dev)
@@ -440,6 +477,15 @@ def bench_config5(args):
     }
     if cpu is not None:
         line["cpu_baseline"] = cpu
+    if args.dump_outputs:
+        # the last timed sweep: the summed report fields every UtilityReport
+        # is assembled from, and the per-partition statistics / errors / keep
+        # probabilities (a seeded sample of the partitions)
+        _dump(args.dump_outputs, {"report_fields": run.rep})
+        per = {"raw_statistics": run.raw_all, "errors": run.err_all}
+        if run.keep_all is not None:
+            per["keep_probability"] = run.keep_all
+        _dump(args.dump_outputs, per, "_partitions")
     print(json.dumps(line), flush=True)
 
 
@@ -458,15 +504,21 @@ def main():
     ap.add_argument("--mcpp", type=int, default=None)
     ap.add_argument("--pid-cap", type=float, default=1000.0,
                     help="config4: cap of the Pareto weight of one privacy id")
+    ap.add_argument("--full", action="store_true",
+                    help="also: CPU baseline, pipelined timing, per-stage table, the call "
+                         "without the privacy-id range, PMC traffic, multi-rank self-check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy")
     ap.add_argument("--cpu-records", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without its CPU baseline")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl")
     ap.add_argument("--exchange", choices=["auto", "reduce_scatter", "all_to_all"],
                     default="auto")
     ap.add_argument("--check-single", action="store_true",
                     help="(default for N > 1; kept for compatibility)")
     ap.add_argument("--no-check-single", action="store_true",
-                    help="multi-rank: skip the one-rank equality check after timing")
+                    help="multi-rank --full: skip the one-rank equality check after timing")
     ap.add_argument("--check-records", type=int, default=None,
                     help="records per rank in the one-rank check (default min(records, 1e8, "
                          "4e8 / N))")
@@ -492,9 +544,9 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
-    # the CPU baseline runs first, before this process touches the GPU
+    # the CPU baseline (--full) runs first, before this process touches the GPU
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, args.partitions)
     # device_count() does not initialise the GPU; gloo ranks may share one
     ndev = max(1, torch.cuda.device_count())
@@ -524,12 +576,20 @@ def main():
     params = make_params(args)
     public = range(P) if (c4 and args.public) else None
 
+    released = [0]
+
+    def release(res):
+        # fresh per release, the same from run to run (and on every rank)
+        res.nonce = NONCE0 + released[0]
+        released[0] += 1
+        return res.materialize(gather=False)
+
     def step(resolve=True):
         acc = pdp.NaiveBudgetAccountant(1.0, 1e-6)
         eng = pdp.DPEngine(acc, backend)
         res = eng.aggregate(cols, params, ex, public_partitions=public)
         acc.compute_budgets()
-        out = res.materialize(gather=False)
+        out = release(res)
         if resolve:
             # every timed release is read back as a caller would: its kept
             # count (one host synchronisation), its compaction tail and the
@@ -558,25 +618,36 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # headline: releases read one by one; beside it (labelled, not the
-    # value), releases enqueued back to back without reading them, where each
-    # one's tail overlaps the next one's host work
+    # headline: releases read one by one
     wall, dev_ms, res, out = timed(True)
-    wall_pl, _, _, _ = timed(False)
-    # the per-stage breakdown from one more, untimed step: reading a step's
-    # stage events is host work the timed steps do not include
-    res, out = step()
-    stage_tot = backend.ctx.stage_times()
-    # untimed: what a caller that does not declare the privacy-id range pays
-    # on top (the device min / max pass over the pid column, stage "pidrange")
-    nohint = pdp.ColumnarData(pid=pid, pk=pk, value=val, n_partitions=P,
-                              record_id_offset=rank * args.records)
-    acc_nh = pdp.NaiveBudgetAccountant(1.0, 1e-6)
-    r_nh = pdp.DPEngine(acc_nh, backend).aggregate(nohint, params, ex, public_partitions=public)
-    acc_nh.compute_budgets()
-    r_nh.materialize(gather=False)
-    pidrange_ms = backend.ctx.stage_times().get("pidrange")
-    del r_nh, nohint
+    if args.dump_outputs:
+        # what the caller of the last timed step received (this rank's slice)
+        _dump(args.dump_outputs, {"partition_ids": out.partition_ids, "values": out.values},
+              f"_rank{rank}" if world > 1 else "")
+    kept = int(out.partition_ids.numel())
+    wall_pl = 0.0
+    stage_tot = pidrange_ms = None
+    if args.full:
+        # beside the headline (labelled, not the value): releases enqueued
+        # back to back without reading them, where each one's tail overlaps
+        # the next one's host work
+        wall_pl, _, _, _ = timed(False)
+        # the per-stage breakdown from one more, untimed step: reading a step's
+        # stage events is host work the timed steps do not include
+        res, out = step()
+        stage_tot = backend.ctx.stage_times()
+        # untimed: what a caller that does not declare the privacy-id range pays
+        # on top (the device min / max pass over the pid column, stage "pidrange")
+        nohint = pdp.ColumnarData(pid=pid, pk=pk, value=val, n_partitions=P,
+                                  record_id_offset=rank * args.records)
+        acc_nh = pdp.NaiveBudgetAccountant(1.0, 1e-6)
+        r_nh = pdp.DPEngine(acc_nh, backend).aggregate(nohint, params, ex,
+                                                       public_partitions=public)
+        acc_nh.compute_budgets()
+        r_nh.materialize(gather=False)
+        pidrange_ms = backend.ctx.stage_times().get("pidrange")
+        del r_nh, nohint
+        kept = int(out.partition_ids.numel())
     per_rank = [[wall, dev_ms, wall_pl]]
     if group is not None:
         cdev = dev if args.dist_backend == "nccl" else torch.device("cpu")
@@ -590,38 +661,39 @@ def main():
     ms_per_step = wall / args.steps * 1e3
     total_records = args.records * world
     value = total_records / (wall / args.steps)
-    kept = int(out.partition_ids.numel())
-    lp = res.last_partials
-    kept_pairs = int(lp["rows"].sum().item())
-    kept_recs = int(lp["count"].sum().item())
-    stage_ms = dict(stage_tot)
-    path_ms = sum(v for k, v in stage_ms.items() if k != "bounding")
     # 24 B per record; MEAN+VARIANCE (config 4) adds 40 B per
     # partition of partials (rows, count, nsum, nsq + the noised outputs)
     algo_bytes = ALGO_BYTES_PER_RECORD * args.records + (40 * P if c4 else 0)
-    # record / item formats of the two workloads: config
-    # 4 packs 12-byte R12 records (70 key bits) and 24-byte ItemV items
-    # (MEAN + VARIANCE without SUM: rows, count, nsum, nsq partials)
-    n_accum = 4 if c4 else 3
-    rec_bytes = 12 if c4 else 8
-    item_bytes = 24 if c4 else 16
-    # the bounding kernels as one stage (the sort kernel's wide pass, the
-    # medium and global-memory kernels, the heavy-id filter)
-    bparts = [k for k in stage_ms if k in ("heavy", "bound", "bound.wide", "bound.medium", "bound.tail")]
-    if bparts:
-        stage_ms["bounding"] = sum(stage_ms[k] for k in bparts)
     # headline: the whole path (24 B/record over the device time per step)
     achieved = algo_bytes / (dev_ms_max * 1e-3) / 1e9
     dflt = _default_workload(args, c4)
-    tj, tsrc = _traffic(c4, args.records, dflt)
+    tj = tsrc = None
     kernels = {}
-    for st, ms in stage_ms.items():
-        b = stage_design_bytes(st, args.records, rec_bytes, item_bytes, kept_recs, kept_pairs,
-                               P, n_accum)
-        kernels[st] = {"ms": round(ms, 4)}
-        if b is not None and ms > 0:
-            kernels[st].update(design_bytes=b, achieved_gbs=round(b / (ms * 1e-3) / 1e9, 1),
-                               frac=round(b / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
+    if args.full:
+        lp = res.last_partials
+        kept_pairs = int(lp["rows"].sum().item())
+        kept_recs = int(lp["count"].sum().item())
+        stage_ms = dict(stage_tot)
+        # record / item formats of the two workloads: config
+        # 4 packs 12-byte R12 records (70 key bits) and 24-byte ItemV items
+        # (MEAN + VARIANCE without SUM: rows, count, nsum, nsq partials)
+        n_accum = 4 if c4 else 3
+        rec_bytes = 12 if c4 else 8
+        item_bytes = 24 if c4 else 16
+        # the bounding kernels as one stage (the sort kernel's wide pass, the
+        # medium and global-memory kernels, the heavy-id filter)
+        bparts = [k for k in stage_ms
+                  if k in ("heavy", "bound", "bound.wide", "bound.medium", "bound.tail")]
+        if bparts:
+            stage_ms["bounding"] = sum(stage_ms[k] for k in bparts)
+        tj, tsrc = _traffic(c4, args.records, dflt)
+        for st, ms in stage_ms.items():
+            b = stage_design_bytes(st, args.records, rec_bytes, item_bytes, kept_recs,
+                                   kept_pairs, P, n_accum)
+            kernels[st] = {"ms": round(ms, 4)}
+            if b is not None and ms > 0:
+                kernels[st].update(design_bytes=b, achieved_gbs=round(b / (ms * 1e-3) / 1e9, 1),
+                                   frac=round(b / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
     if c4:
         workload = (f"configs[3]: {args.records:.0e} records / {args.pids:.0e} privacy ids "
                     f"(Pareto(1.2) records per id, weight cap {args.pid_cap:g}) / {P:.0e} "
@@ -636,11 +708,8 @@ def main():
         "metric": METRIC, "value": value, "unit": "records/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "ms_per_step_pipelined": wall_pl / args.steps * 1e3,
         "ms_per_step_note": "ms_per_step / value: each release read back (kept count, one host "
-                            "sync) inside its step; ms_per_step_pipelined: the same releases "
-                            "enqueued back to back without reading them (each tail overlaps "
-                            "the next release's host work), not the headline",
+                            "sync) inside its step",
         "dtype": "f64", "data": "synthetic (device-generated Zipf keys, uniform values)",
         "config": {"workload": workload,
                    "records_per_gpu": args.records, "privacy_ids_per_gpu": args.pids,
@@ -652,23 +721,30 @@ def main():
                    "parallelism": f"pid-sharded x{world}",
                    # caller metadata, like n_partitions: the timed calls skip
                    # the device min / max of the pid column (its cost, from an
-                   # untimed call without the hint: kernels["pidrange_untimed"])
+                   # untimed call without the hint: --full, kernels["pidrange_untimed"])
                    "privacy_id_range_supplied": True},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS,
-                     "traffic": (tj["bytes_per_step"] if tj else None),
+                     "traffic": None,
                      "kernel": "whole path (dpg_bound_aggregate + select/noise + compact)",
                      "device_ms": dev_ms_max,
                      "algorithmic_bytes": algo_bytes,
                      "note": "achieved = 24 B/record x records (+ 40 B/partition for MEAN+VARIANCE, "
                              "SURVEY.md 8(d)) / device time per step (HIP "
-                             "events on the kernels' stream, max over ranks); traffic = PMC "
-                             "HBM bytes per step (FETCH_SIZE x calibrated factor + WRITE_SIZE) "
-                             f"from {tsrc}"},
-        "kernels": kernels,
-        "kept_partitions": kept, "kept_pairs": kept_pairs, "kept_records": kept_recs,
+                             "events on the kernels' stream, max over ranks)"},
+        "kept_partitions": kept,
         "lib_sha256": _lib_sha(),
     }
+    if args.full:
+        line["ms_per_step_pipelined"] = wall_pl / args.steps * 1e3
+        line["ms_per_step_note"] += (
+            "; ms_per_step_pipelined: the same releases enqueued back to back without reading "
+            "them (each tail overlaps the next release's host work), not the headline")
+        line["roofline"]["traffic"] = tj["bytes_per_step"] if tj else None
+        line["roofline"]["note"] += ("; traffic = PMC HBM bytes per step (FETCH_SIZE x calibrated "
+                                     f"factor + WRITE_SIZE) from {tsrc}")
+        line["kernels"] = kernels
+        line.update(kept_pairs=kept_pairs, kept_records=kept_recs)
     if pidrange_ms is not None:
         b = stage_design_bytes("pidrange", args.records, rec_bytes, item_bytes, 0, 0, P, n_accum)
         kernels["pidrange_untimed"] = {
@@ -689,7 +765,7 @@ def main():
             "exchange": res.last_exchange,
             "rank_ms_per_step": [r[0] / args.steps * 1e3 for r in per_rank],
             "rank_device_ms": [r[1] for r in per_rank]}
-        if not args.no_check_single:
+        if args.full and not args.no_check_single:
             line["distributed"]["check_single"] = check_single(
                 args, (pid, pk, val), params, public, world, rank, dev, group)
     if rank == 0:

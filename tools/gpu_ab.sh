@@ -7,7 +7,7 @@ set -o pipefail
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 VARIANTS=${VARIANTS:-libdpg_b.so}
-BA=${BENCH_ARGS:-}
+BA="--full ${BENCH_ARGS:-}"  # the per-stage table printed below is part of the --full line
 T=${TAG:-ab}
 for i in 1 2; do
   timeout -k 10 300 python -u bench.py --steps 4 --warmup 1 --no-cpu-baseline $BA > gpurun_out/${T}_a$i.json 2> gpurun_out/${T}_a$i.err || { echo "a failed"; tail -5 gpurun_out/${T}_a$i.err; exit 1; }

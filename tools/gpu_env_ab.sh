@@ -12,7 +12,7 @@ VARIANTS=${VARIANTS:-base:DPG_X=0}
 for i in 1 2; do
   for v in $VARIANTS; do
     nm=${v%%:*}; kv=${v#*:}
-    env ${kv//,/ } timeout -k 10 300 python -u bench.py --steps ${STEPS:-4} --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > $O/${nm}_$i.json 2> $O/${nm}_$i.err || { echo "$nm failed"; tail -5 $O/${nm}_$i.err; exit 1; }
+    env ${kv//,/ } timeout -k 10 300 python -u bench.py --steps ${STEPS:-4} --warmup 1 --full --no-cpu-baseline ${BENCH_ARGS:-} > $O/${nm}_$i.json 2> $O/${nm}_$i.err || { echo "$nm failed"; tail -5 $O/${nm}_$i.err; exit 1; }
   done
 done
 O=$O python3 - <<'PY'

@@ -11,7 +11,7 @@ mkdir -p $O
 timeout -k 10 900 python -u -m pytest tests/test_gpu_envelope.py tests/test_gpu_configs.py tests/test_gpu_parity.py \
     -m gpu -x -v --timeout 300 --timeout-method thread > $O/pytest.log 2>&1 || { tail -40 $O/pytest.log; exit 1; }
 tail -2 $O/pytest.log
-B="timeout -k 10 400 python -u bench.py --steps 5 --warmup 1 --no-cpu-baseline"
+B="timeout -k 10 400 python -u bench.py --steps 5 --warmup 1 --full --no-cpu-baseline"
 $B > $O/bench_c2.json 2> $O/bench_c2.err || { tail -5 $O/bench_c2.err; exit 1; }
 $B --records 1000000000 --pids 1000000 > $O/bench_u1e6.json 2> $O/bench_u1e6.err || { tail -5 $O/bench_u1e6.err; exit 1; }
 $B --records 2000000000 --pids 20000000 > $O/bench_n2e9.json 2> $O/bench_n2e9.err || { tail -5 $O/bench_n2e9.err; exit 1; }

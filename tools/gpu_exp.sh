@@ -4,6 +4,7 @@
 set -o pipefail
 export TMPDIR=/tmp
 mkdir -p gpurun_out
+BENCH_ARGS="--full $BENCH_ARGS"  # the per-stage table printed below is part of the --full line
 run() {  # name, env assignments, lib
   env $2 DPG_LIB_PATH=pipelinedp_amd/lib/$3 timeout -k 10 300 python -u bench.py --steps 4 --warmup 1 --no-cpu-baseline $BENCH_ARGS > gpurun_out/exp_$1_$i.json 2> gpurun_out/exp_$1_$i.err || { echo "$1 failed"; tail -5 gpurun_out/exp_$1_$i.err; exit 1; }
 }

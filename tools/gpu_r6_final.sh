@@ -43,17 +43,17 @@ python3 tools/kstats.py $(find $O/kt -name "*kernel_stats.csv" | head -1) 10
 fi
 [ -n "$SKIP_BENCH" ] && { echo done; exit 0; }
 summ() { python3 -c "import json,sys; d=json.load(open('$1')); print('$2', round(d['ms_per_step'],2), 'frac', round(d['roofline']['frac'],4), 'traffic', d['roofline'].get('traffic'), 'cpu', (d.get('cpu_baseline') or {}).get('value'))"; }
-timeout -k 10 600 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err || { echo bench failed; tail -20 $O/bench_c2.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err || { echo bench failed; tail -20 $O/bench_c2.err; exit 1; }
 summ $O/bench_c2.json c2
-timeout -k 10 600 python bench.py --workload config4 --steps 4 --warmup 1 > $O/bench_c4.json 2> $O/bench_c4.err || { echo c4 failed; tail -20 $O/bench_c4.err; exit 1; }
+timeout -k 10 600 python bench.py --workload config4 --steps 4 --warmup 1 --full > $O/bench_c4.json 2> $O/bench_c4.err || { echo c4 failed; tail -20 $O/bench_c4.err; exit 1; }
 summ $O/bench_c4.json c4
-timeout -k 10 600 python bench.py --workload config4 --public --steps 4 --warmup 1 > $O/bench_c4p.json 2> $O/bench_c4p.err || { echo c4p failed; tail -20 $O/bench_c4p.err; exit 1; }
+timeout -k 10 600 python bench.py --workload config4 --public --steps 4 --warmup 1 --full > $O/bench_c4p.json 2> $O/bench_c4p.err || { echo c4p failed; tail -20 $O/bench_c4p.err; exit 1; }
 summ $O/bench_c4p.json c4p
-timeout -k 10 400 python bench.py --workload config5 --steps 3 --warmup 1 > $O/bench_c5.json 2> $O/bench_c5.err || { echo c5 failed; tail -20 $O/bench_c5.err; exit 1; }
+timeout -k 10 400 python bench.py --workload config5 --steps 3 --warmup 1 --full > $O/bench_c5.json 2> $O/bench_c5.err || { echo c5 failed; tail -20 $O/bench_c5.err; exit 1; }
 summ $O/bench_c5.json c5
-timeout -k 10 400 python bench.py --records 1000000000 --pids 1000000 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_u1e6.json 2> $O/bench_u1e6.err || { echo u1e6 failed; tail -20 $O/bench_u1e6.err; exit 1; }
+timeout -k 10 400 python bench.py --records 1000000000 --pids 1000000 --steps 3 --warmup 1 --full --no-cpu-baseline > $O/bench_u1e6.json 2> $O/bench_u1e6.err || { echo u1e6 failed; tail -20 $O/bench_u1e6.err; exit 1; }
 summ $O/bench_u1e6.json u1e6
-timeout -k 10 400 python bench.py --records 2000000000 --pids 20000000 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_n2e9.json 2> $O/bench_n2e9.err || { echo n2e9 failed; tail -20 $O/bench_n2e9.err; exit 1; }
+timeout -k 10 400 python bench.py --records 2000000000 --pids 20000000 --steps 3 --warmup 1 --full --no-cpu-baseline > $O/bench_n2e9.json 2> $O/bench_n2e9.err || { echo n2e9 failed; tail -20 $O/bench_n2e9.err; exit 1; }
 summ $O/bench_n2e9.json n2e9
 timeout -k 10 300 python -u tools/ua_timing.py > $O/ua_timing.log 2>&1 || { echo ua_timing failed; tail -5 $O/ua_timing.log; exit 1; }
 tail -2 $O/ua_timing.log
