@@ -622,6 +622,11 @@ BoundParams to_bound(const dpg_bound_params *p, uint64_t seed) {
     // working set; DPG_EARLY_DEFER=0: off)
     const char *ed = std::getenv("DPG_EARLY_DEFER");
     b.defer_est = (ed && std::atoi(ed) == 0) ? 0.0f : 1.25f * 256.0f;
+    // test hook: priority bits the 32-bit sort key keeps at most (2: nearly
+    // every chunk fails its order check and takes the float64 network)
+    b.sort32_ppb = 0;
+    if (const char *e = std::getenv("DPG_DEBUG_SORT32_PPB"))
+        b.sort32_ppb = (uint32_t)std::max(0, std::min(32, std::atoi(e)));
     return b;
 }
 
@@ -930,6 +935,8 @@ int bound_and_reduce(dpg_ctx *ctx, hipStream_t s, const Plan &pl, const R *recs,
     }
     // zero-length marker stage: which small-chunk kernel bounded this call
     stage(ctx, s, use_sort ? "bound.kernel=sort" : "bound.kernel=hash");
+    // marker: the launch's single-wave passes carry the 32-bit sort network
+    if (use_sort && !wpk && DPG_SORT_U32 && DPG_SORT_PACKED) stage(ctx, s, "bound.sort32");
     if (use_mw) stage(ctx, s, "bound.multiwave");  // marker: wide / medium chunks in dpg_sortmw.h
     stage(ctx, s, "bound");
     if constexpr (!ItemTraits<Item>::preagg) if (use_sort) {
@@ -1095,6 +1102,10 @@ int bound_and_reduce(dpg_ctx *ctx, hipStream_t s, const Plan &pl, const R *recs,
             for (int i = 0; i < np; ++i)
                 std::fprintf(stderr, " %s=%.3f(%.0f%%)", nm[i], hp[i] / 1e6 / gg,
                              100.0 * hp[i] / (tot ? tot : 1));
+            // single-wave sort passes: chunk rounds sorted on 32-bit keys,
+            // and those whose order check sent them to the float64 network
+            if (sortnames && part < 2 && use_sort)
+                std::fprintf(stderr, " sort32=%llu fallback=%llu", hp[12], hp[13]);
             std::fprintf(stderr, "\n");
         }
         if (mdefer) {

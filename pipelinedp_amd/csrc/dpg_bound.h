@@ -51,6 +51,8 @@ struct BoundParams {
     float defer_est;       // sort kernel, narrow / streamed passes: a chunk whose
                            // expected candidates exceed this is deferred before
                            // its pair priorities are drawn (0: off)
+    uint32_t sort32_ppb;   // sort kernel, test hook: priority bits kept in the 32-bit
+                           // sort key at most (0: all that fit, gated by kSort32MinPpb)
 };
 
 // privacy id of a bucket's pid-hash residual
@@ -69,6 +71,7 @@ __device__ __forceinline__ uint64_t pid_of(const BoundParams &bp, uint32_t d1, u
 struct PhaseTimer {
     uint64_t last;
     uint64_t pt[12];
+    uint32_t n32, nfb;  // sort kernel: chunks sorted on 32-bit keys, those that fell back
 };
 #else
 struct PhaseTimer {};
@@ -97,6 +100,7 @@ __device__ __forceinline__ void timer_start(const BoundParams &bp, PhaseTimer &t
 #ifdef DPG_PHASE_TIMING
     tm.last = bp.phase_cyc ? __builtin_amdgcn_s_memtime() : 0;
     for (int k = 0; k < 12; ++k) tm.pt[k] = 0;
+    tm.n32 = tm.nfb = 0;
 #else
     (void)bp;
     (void)tm;
@@ -106,9 +110,25 @@ __device__ __forceinline__ void timer_flush(const BoundParams &bp, const PhaseTi
 #ifdef DPG_PHASE_TIMING
     if (bp.phase_cyc && threadIdx.x == 0)
         for (int k = 0; k < 12; ++k) atomicAdd(&bp.phase_cyc[k], (unsigned long long)tm.pt[k]);
+    // words 12, 13 of the kernel's 16: the 32-bit sort's chunk counts
+    if (bp.phase_cyc && threadIdx.x == 0 && tm.n32) {
+        atomicAdd(&bp.phase_cyc[12], (unsigned long long)tm.n32);
+        atomicAdd(&bp.phase_cyc[13], (unsigned long long)tm.nfb);
+    }
 #else
     (void)bp;
     (void)tm;
+#endif
+}
+// timing build only: one chunk sorted on 32-bit keys (fell_back: its order
+// check failed and the float64 network sorted it again); wave-uniform
+__device__ __forceinline__ void count_sort32(PhaseTimer &tm, bool fell_back) {
+#ifdef DPG_PHASE_TIMING
+    tm.n32 += 1u;
+    tm.nfb += fell_back ? 1u : 0u;
+#else
+    (void)tm;
+    (void)fell_back;
 #endif
 }
 

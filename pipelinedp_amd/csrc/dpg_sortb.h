@@ -23,7 +23,14 @@
 //      whole pairs pass or fail); candidates are compacted into LDS
 //   S  bitonic sort of the candidates' (skey, record index) in registers: E =
 //      1, 2, 4 or 8 elements per lane (64 E >= candidates), cross-lane steps
-//      by DPP / ds_swizzle / bpermute
+//      by DPP / ds_swizzle / bpermute.  Up to E = 4 (narrow keys) the sort
+//      runs on packed keys alone that carry the candidate's position, and
+//      the full keys and record indices are read back by position: first on
+//      32-bit keys (pid slot | top priority bits | position: one v_med3_u32
+//      per cross-lane compare-exchange) when those keep >= kSort32MinPpb
+//      priority bits; a result whose full keys do not ascend (two pairs tied
+//      in the kept bits), or a chunk with fewer bits, sorts float64-packed
+//      64-bit keys (v_min_f64 / v_max_f64); a tie even there, (key, payload)
 //   P  pair starts, pair ordinals (wave scan), pair rank inside the pid; a
 //      filtered pid that shows fewer than mpc candidate pairs restarts the
 //      chunk with all of its records, re-read from HBM (rare); a pair is
@@ -342,6 +349,98 @@ __device__ __forceinline__ void bitonic_sort_keys_f64(uint64_t (&k)[E]) {
     }
 }
 
+// The same network over 32-bit keys (sort_chunk's narrow keys: pid slot |
+// top priority bits | candidate position, unique; padding 0xFFFFFFFF).  An
+// in-lane compare-exchange is v_min_u32 + v_max_u32.  A cross-lane one,
+// "keep the minimum on the lower lane, the maximum on the upper", is ONE
+// v_med3_u32 of (mine, partner's, c) with c = 0 on the lower lane and ~0 on
+// the upper: med3(a, b, 0) = min(a, b), med3(a, b, ~0) = max(a, b).  c is one
+// sign-extended lane bit per step, shared by the E elements, and the partner
+// comes by one xlane (v_mov_b32_dpp for lane ^ 1, 2, 3, 7, 15: 13 of the 21
+// cross-lane steps): ~34 VALU per element against ~126 of the float64 form.
+// (Inline asm: the compiler forms med3 from min / max of constants only.)
+#ifndef DPG_SORT_U32
+#define DPG_SORT_U32 1  // 0: the float64-packed network for every packed chunk
+#endif
+// the 32-bit key is used when it keeps at least this many priority bits
+// (fewer: two pairs of one pid tie too often, and the chunk sorts twice).
+// Same-box A/Bs (profiles/r7): config 2 with the kept bits capped -- bounding
+// 5.58 ms at 20 bits (0.1 % of the chunks sort twice), 5.59 at 18 (0.4 %),
+// 5.60 at 16 (1.8 %), 5.70 at 14 (7 %), 5.91 at 12 (25 %), 6.38 at 10 (66 %)
+// against 6.13 with the float64 network alone; chunks of many tiny pids that
+// stay in this pass (7 slot bits, E = 4: 17 bits) 5.64 -> 5.40 ms.  17 is the
+// fewest bits a chunk of today's passes keeps (7 slot + 8 position bits), so
+// every one takes the 32-bit key first; the gate is for wider layouts.
+constexpr uint32_t kSort32MinPpb = 17;
+
+__device__ __forceinline__ uint32_t med3_u32(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r;
+    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
+template <int E>
+__device__ __forceinline__ void bitonic_sort_keys_u32(uint32_t (&k)[E]) {
+    constexpr int LOG_S = E == 1 ? 6 : E == 2 ? 7 : E == 4 ? 8 : 9;
+    constexpr int LOG_E = LOG_S - 6;
+    uint32_t lid = __lane_id();
+    asm volatile("" : "+v"(lid));
+    auto cex = [&](int j, int j2) {
+        const uint32_t a = k[j], b = k[j2];
+        k[j] = min(a, b);
+        k[j2] = max(a, b);
+    };
+    // 0 where lane bit b is clear (the lower index of the step), else ~0
+    auto upper = [&](int b) { return (uint32_t)((int32_t)(lid << (31 - b)) >> 31); };
+#pragma unroll
+    for (int lk = 1; lk <= LOG_S; ++lk) {
+        const int kk = 1 << lk;
+        if (lk <= LOG_E) {
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+                const int j2 = j ^ (kk - 1);
+                if (j < j2) cex(j, j2);
+            }
+        } else {
+            const int m = (kk >> LOG_E) - 1;       // partner lane = lane ^ m, slot E-1-j
+            const uint32_t c = upper(lk - LOG_E - 1);  // bit (m + 1) >> 1
+            uint32_t y[E];
+#pragma unroll
+            for (int j = 0; j < E; ++j) y[j] = xlane(k[E - 1 - j], m);
+#pragma unroll
+            for (int j = 0; j < E; ++j) k[j] = med3_u32(k[j], y[j], c);
+        }
+#pragma unroll
+        for (int ls = lk - 2; ls >= 0; --ls) {
+            const int sd = 1 << ls;
+            if (ls < LOG_E) {
+#pragma unroll
+                for (int j = 0; j < E; ++j)
+                    if (!(j & sd)) cex(j, j | sd);
+            } else {
+                const uint32_t c = upper(ls - LOG_E);  // partner lane = lane ^ (sd >> LOG_E)
+#pragma unroll
+                for (int j = 0; j < E; ++j) k[j] = med3_u32(k[j], xlane(k[j], sd >> LOG_E), c);
+            }
+        }
+    }
+}
+
+// pid-slot bits of a chunk's 32-bit sort keys: those of its largest occupied
+// slot (at least one), from the occupancy ballots of the slots' two halves
+__device__ __forceinline__ uint32_t slot_bits(uint64_t occ_lo, uint64_t occ_hi) {
+    const uint32_t qmax = occ_hi ? 127u - (uint32_t)__builtin_clzll(occ_hi)
+                                 : 63u - (uint32_t)__builtin_clzll(occ_lo | 1ull);
+    return 32u - (uint32_t)__builtin_clz(qmax | 1u);
+}
+// ... recomputed from the per-slot record counts (restart rounds, whose
+// phase A does not walk the slots)
+__device__ __forceinline__ uint32_t slot_bits(const uint32_t *pidc) {
+    static_assert(kWCq == 128, "two ballots cover the pid slots");
+    const uint32_t lane = __lane_id();
+    return slot_bits(__ballot(pidc[lane] > 0), __ballot(pidc[lane + 64u] > 0));
+}
+
 // Sorts the nc candidates and bounds them (phases S, P, M, F of the header).
 // Returns kRoundRestart when the chunk must restart: the filtered pids short
 // of mpc candidate pairs have had their bound lifted (their CBND set to
@@ -359,7 +458,8 @@ constexpr int kRoundRestart = 0, kRoundDone = 1, kRoundDefer = 2;
 template <class Item, class R, int E, bool kWPk, bool kLex, int kC>
 __device__ __forceinline__ int sort_chunk(uint32_t nc, char *smem, const BoundParams &bp,
                                            bool last_round, uint32_t hbound, uint32_t hidx,
-                                           Item *items, uint32_t &nitems, PhaseTimer &clk) {
+                                           Item *items, uint32_t &nitems, PhaseTimer &clk,
+                                           uint32_t qb) {
     using L = SortLayout<Item, R, kWPk, kC>;
     static_assert(64 * E <= kC || E == 1, "sort width beyond the working set");
     constexpr bool kVar = ItemTraits<Item>::var;
@@ -401,7 +501,61 @@ __device__ __forceinline__ int sort_chunk(uint32_t nc, char *smem, const BoundPa
     full[lane] = 0;
     full[lane + 64u] = 0;
     bool sorted_packed = false;
-    if constexpr (!kWPk && !kLex && E <= 4 && DPG_SORT_PACKED) {
+    // the candidates' full keys and record indices, in the order of the
+    // sorted positions (pos < 64 E <= 512), and whether those keys ascend
+    auto read_back = [&](auto pos_of) {
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            const uint32_t i = lane * E + j;
+            const uint32_t pos = min(pos_of(j), L::CAP - 1);
+            k[j] = i < nc ? ckey[pos] : kSkPad;
+            o[j] = i < nc ? cidx[pos] : 0u;
+        }
+        const uint64_t pl = (uint64_t)__shfl_up((long long)k[E - 1], 1, 64);
+        bool bad = false;
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            const uint32_t i = lane * E + j;
+            bad |= i > 0 && i < nc && k[j] < (j ? k[j - 1] : pl);
+        }
+        return __ballot(bad) == 0;
+    };
+    if constexpr (!kWPk && !kLex && E <= 4 && DPG_SORT_PACKED && DPG_SORT_U32) {
+        // 32-bit keys alone (one VALU per cross-lane compare-exchange, see
+        // bitonic_sort_keys_u32): pid slot (qb bits: those of the chunk's
+        // largest occupied slot) | top ppb = 32 - qb - pb bits of the pair
+        // priority | candidate position (pb = 6 + log2 E bits); no partition
+        // key.  The full keys and record indices are read back by position.
+        // Records of one pair stay in position order (their full keys are
+        // equal).  Two pairs of one pid whose priorities agree in the kept
+        // bits (~n^2 / 2^(ppb + 1) per pid of n candidate pairs) come out in
+        // position order: unless that happens to be their key order, the
+        // full keys do not ascend -- the check is exact -- and the chunk is
+        // sorted again by the float64 network below.  With fewer than
+        // kSort32MinPpb bits left the float64 network would sort the chunk
+        // in the first place.
+        constexpr uint32_t pb = E == 1 ? 6 : E == 2 ? 7 : 8;
+        const uint32_t room = 32u - pb - qb;  // >= 17
+        const uint32_t ppb = bp.sort32_ppb ? min(room, bp.sort32_ppb) : room;
+        if (bp.sort32_ppb || room >= kSort32MinPpb) {
+            uint32_t k32[E];
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+                const uint32_t i = lane * E + j;
+                const uint32_t q = (uint32_t)(k[j] >> 56);
+                const uint32_t pp = (uint32_t)(k[j] >> kSkPkBits);
+                k32[j] = i < nc ? ((q << (32u - qb)) | ((pp >> (32u - ppb)) << pb) | i) : 0xFFFFFFFFu;
+            }
+            bitonic_sort_keys_u32<E>(k32);
+            sorted_packed = read_back([&](int j) { return k32[j] & (64u * E - 1u); });
+            count_sort32(clk, !sorted_packed);
+            if (!sorted_packed) {
+#pragma unroll
+                for (int j = 0; j < E; ++j) k[j] = ckey[min(lane * E + j, L::CAP - 1)];
+            }
+        }
+    }
+    if constexpr (!kWPk && !kLex && E <= 4 && DPG_SORT_PACKED) if (!sorted_packed) {
         // keys alone (2 VALU per in-lane compare-exchange, see
         // bitonic_sort_keys_f64): tag bits 01 | pid slot (7 bits) | top
         // min(32, 45 - pkbits) bits of the pair priority | pk | candidate
@@ -424,21 +578,7 @@ __device__ __forceinline__ int sort_chunk(uint32_t nc, char *smem, const BoundPa
                              : kSkPadF;
         }
         bitonic_sort_keys_f64<E>(pk64);
-#pragma unroll
-        for (int j = 0; j < E; ++j) {
-            const uint32_t i = lane * E + j;
-            const uint32_t pos = (uint32_t)pk64[j] & 511u;
-            k[j] = i < nc ? ckey[min(pos, L::CAP - 1)] : kSkPad;
-            o[j] = i < nc ? cidx[min(pos, L::CAP - 1)] : 0u;
-        }
-        const uint64_t pl = (uint64_t)__shfl_up((long long)k[E - 1], 1, 64);
-        bool bad = false;
-#pragma unroll
-        for (int j = 0; j < E; ++j) {
-            const uint32_t i = lane * E + j;
-            bad |= i > 0 && i < nc && k[j] < (j ? k[j - 1] : pl);
-        }
-        sorted_packed = __ballot(bad) == 0;
+        sorted_packed = read_back([&](int j) { return (uint32_t)pk64[j] & 511u; });
         if (!sorted_packed) {
 #pragma unroll
             for (int j = 0; j < E; ++j) {
@@ -679,6 +819,7 @@ __device__ __forceinline__ int sort_round(const R (&r)[kWRPT], uint32_t n, uint3
         sk[k] = ((uint64_t)q << 56) | (key & pkmask);
         ix[k] = RecOps<R>::idx(r[k], f);
     }
+    uint32_t qb = 0;  // pid-slot bits of the 32-bit sort keys (slot_bits)
     if constexpr (kFirst) {
 #pragma unroll
         for (int k = 0; k < kWRPT && k < (int)kn; ++k)
@@ -687,6 +828,7 @@ __device__ __forceinline__ int sort_round(const R (&r)[kWRPT], uint32_t n, uint3
         // pid hash and candidate bound of the occupied slots (compacted)
         const float cmul = bp.cand_mul;
         uint32_t nocc = 0;
+        uint64_t occm[kWCq / 64];
 #pragma unroll
         for (int j = 0; j < (int)(kWCq / 64); ++j) {
             const uint32_t qq = lane + 64u * j;
@@ -694,7 +836,9 @@ __device__ __forceinline__ int sort_round(const R (&r)[kWRPT], uint32_t n, uint3
             const uint64_t bo = __ballot(occ);
             if (occ) olist[nocc + lanes_below(bo)] = qq;
             nocc += (uint32_t)__popcll(bo);
+            occm[j] = bo;
         }
+        if constexpr (DPG_SORT_U32 != 0) qb = slot_bits(occm[0], occm[1]);
         wave_sync();
         float est = 0.0f;  // expected candidates: all records of unfiltered pids, ~cmul of the others
         for (uint32_t o = 0; o < nocc; o += 64) {
@@ -717,6 +861,8 @@ __device__ __forceinline__ int sort_round(const R (&r)[kWRPT], uint32_t n, uint3
             for (int o = 32; o > 0; o >>= 1) est += __shfl_xor(est, o, 64);
             if (bp.defer_est > 0.0f && est > bp.defer_est) return kRoundDefer;
         }
+    } else if constexpr (DPG_SORT_U32 != 0) {
+        qb = slot_bits(pidc);  // a restart round: the first round's counts stand
     }
     uint32_t nc = 0;
     {
@@ -754,16 +900,18 @@ __device__ __forceinline__ int sort_round(const R (&r)[kWRPT], uint32_t n, uint3
     constexpr bool kLex = kWide && kWPk;
     int st;
     if (nc <= 64) {
-        st = sort_chunk<Item, R, 1, kWPk, kLex, L::CAP>(nc, smem, bp, last, hbound, hidx, items, nitems, clk);
+        st = sort_chunk<Item, R, 1, kWPk, kLex, L::CAP>(nc, smem, bp, last, hbound, hidx, items, nitems,
+                                                        clk, qb);
     } else if (nc <= 128 || (!kWide && kC <= 128)) {
-        st = sort_chunk<Item, R, 2, kWPk, kLex, L::CAP>(nc, smem, bp, last, hbound, hidx, items, nitems, clk);
+        st = sort_chunk<Item, R, 2, kWPk, kLex, L::CAP>(nc, smem, bp, last, hbound, hidx, items, nitems,
+                                                        clk, qb);
     } else if constexpr (kWide || kC > 128) {
         if (!kWide || nc <= 256)
             st = sort_chunk<Item, R, 4, kWPk, kLex, L::CAP>(nc, smem, bp, last, hbound, hidx, items, nitems,
-                                                    clk);
+                                                    clk, qb);
         else
             st = sort_chunk<Item, R, kWide ? 8 : 4, kWPk, kLex, L::CAP>(nc, smem, bp, last, hbound, hidx,
-                                                                items, nitems, clk);
+                                                                items, nitems, clk, qb);
     }
     wave_sync();
     return st;
@@ -829,6 +977,7 @@ __device__ __forceinline__ int stream_round(const R *base, uint32_t n, uint32_t 
 #pragma unroll
         for (int k = 0; k < kWRPT; ++k) r[k] = base[p0 + min(lane + 64u * k, m - 1)];
     };
+    uint32_t qb = 0;  // pid-slot bits of the 32-bit sort keys (slot_bits)
     if constexpr (kFirst) {
         for (uint32_t p0 = 0; p0 < n; p0 += kWCap) {
             const uint32_t m = min(n - p0, (uint32_t)kWCap);
@@ -844,6 +993,7 @@ __device__ __forceinline__ int stream_round(const R *base, uint32_t n, uint32_t 
         const float cmul = bp.cand_mul;
         const float big = fmaxf(cmul, fminf(kStreamMul * cmul, 0.5f * (float)kC));
         uint32_t nocc = 0;
+        uint64_t occm[kWCq / 64];
 #pragma unroll
         for (int j = 0; j < (int)(kWCq / 64); ++j) {
             const uint32_t qq = lane + 64u * j;
@@ -851,7 +1001,9 @@ __device__ __forceinline__ int stream_round(const R *base, uint32_t n, uint32_t 
             const uint64_t bo = __ballot(occ);
             if (occ) olist[nocc + lanes_below(bo)] = qq;
             nocc += (uint32_t)__popcll(bo);
+            occm[j] = bo;
         }
+        if constexpr (DPG_SORT_U32 != 0) qb = slot_bits(occm[0], occm[1]);
         wave_sync();
         float est = 0.0f;  // expected candidates (see sort_round)
         for (uint32_t o = 0; o < nocc; o += 64) {
@@ -871,6 +1023,8 @@ __device__ __forceinline__ int stream_round(const R *base, uint32_t n, uint32_t 
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) est += __shfl_xor(est, o, 64);
         if (bp.defer_est > 0.0f && est > bp.defer_est) return kRoundDefer;
+    } else if constexpr (DPG_SORT_U32 != 0) {
+        qb = slot_bits(pidc);  // a restart round: the first round's counts stand
     }
     uint32_t nc = 0;
     for (uint32_t p0 = 0; p0 < n; p0 += kWCap) {
@@ -902,11 +1056,14 @@ __device__ __forceinline__ int stream_round(const R *base, uint32_t n, uint32_t 
     constexpr bool last = !kFirst;
     int st;
     if (nc <= 64)
-        st = sort_chunk<Item, R, 1, kWPk, false, L::CAP>(nc, smem, bp, last, 0u, 0u, items, nitems, clk);
+        st = sort_chunk<Item, R, 1, kWPk, false, L::CAP>(nc, smem, bp, last, 0u, 0u, items, nitems, clk,
+                                                         qb);
     else if (nc <= 128)
-        st = sort_chunk<Item, R, 2, kWPk, false, L::CAP>(nc, smem, bp, last, 0u, 0u, items, nitems, clk);
+        st = sort_chunk<Item, R, 2, kWPk, false, L::CAP>(nc, smem, bp, last, 0u, 0u, items, nitems, clk,
+                                                         qb);
     else
-        st = sort_chunk<Item, R, 4, kWPk, false, L::CAP>(nc, smem, bp, last, 0u, 0u, items, nitems, clk);
+        st = sort_chunk<Item, R, 4, kWPk, false, L::CAP>(nc, smem, bp, last, 0u, 0u, items, nitems, clk,
+                                                         qb);
     wave_sync();
     return st;
 }
