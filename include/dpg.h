@@ -413,6 +413,30 @@ int dpg_unpack_partials(dpg_ctx *ctx, const double *part, int64_t n_partitions, 
 int dpg_export_error(dpg_ctx *ctx, double *dst, void *stream);
 int dpg_import_error(dpg_ctx *ctx, const double *src, int64_t n, void *stream);
 
+/* ---- multi-GPU: records to the rank that owns their privacy id ----
+ * Bounding is shard-local only if every privacy id lives on one rank.  The
+ * owner of a privacy id is shard(pid) = umulhi((uint32_t)pid * 0x9E3779B1u,
+ * nranks) (distributed.shard_of).  The split below orders one rank's records
+ * by owner for the host's record all-to-all; the check counts the records a
+ * rank holds but does not own.  Replaces the reference's framework shuffle
+ * that groups each privacy id's records before sampling
+ * (contribution_bounders.py:86-92, pipeline_backend.py:264-276).
+ * The split works on tiles of DPG_SHARD_TILE records (csrc/dpg_shard.h). */
+#define DPG_SHARD_MAX_RANKS 64
+/* Stable split of n records by owner rank d = shard(pid), nranks <= DPG_SHARD_MAX_RANKS.
+ * out_*: device arrays of n entries, destination-major: the records of
+ * destination d occupy [sum(counts[0..d)), +counts[d]) in their input order.
+ * value / out_value may both be NULL.  counts: device int64[nranks].
+ * n < 2^31 (else DPG_ERR_UNSUPPORTED); n == 0 gives all-zero counts.
+ * Stream-ordered, no host synchronisation. */
+int dpg_shard_records(dpg_ctx *ctx, const int64_t *pid, const int64_t *pk, const double *value,
+                      int64_t n, int nranks, int64_t *out_pid, int64_t *out_pk,
+                      double *out_value, int64_t *counts, void *stream);
+/* *n_bad (device int64) = number of records with shard(pid) != rank.
+ * Stream-ordered, no host synchronisation. */
+int dpg_check_shard(dpg_ctx *ctx, const int64_t *pid, int64_t n, int nranks, int rank,
+                    int64_t *n_bad, void *stream);
+
 /* Timing/profiling aid: per-stage device time (ms) of the last
  * dpg_bound_aggregate / dpg_preaggregate / dpg_dataset_histograms call,
  * measured with HIP events on its stream (waits for the last event).

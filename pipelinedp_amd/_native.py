@@ -22,9 +22,12 @@ EXPORTED = ("dpg_ctx_create", "dpg_ctx_destroy", "dpg_last_error", "dpg_set_seed
             "dpg_utility_analysis", "dpg_dataset_histograms",
             "dpg_comm_unique_id", "dpg_ctx_create_comm", "dpg_reduce_scatter_partials",
             "dpg_pack_partials", "dpg_unpack_partials", "dpg_export_error",
-            "dpg_import_error")
+            "dpg_import_error", "dpg_shard_records", "dpg_check_shard")
 
 COMM_ID_BYTES = 128  # DPG_COMM_ID_BYTES
+
+SHARD_MAX_RANKS = 64  # DPG_SHARD_MAX_RANKS
+SHARD_TILE = 2048  # DPG_SHARD_TILE (csrc/dpg_shard.h): records per workgroup of the split
 
 HIST_INT_BINS = 16300  # DPG_HIST_INT_BINS
 HIST_SUM_BINS = 10000  # DPG_HIST_SUM_BINS
@@ -199,6 +202,10 @@ def load():
         lib.dpg_export_error.restype = ctypes.c_int
         lib.dpg_import_error.argtypes = [vp, vp, i64, vp]
         lib.dpg_import_error.restype = ctypes.c_int
+        lib.dpg_shard_records.argtypes = [vp, vp, vp, vp, i64, ctypes.c_int, vp, vp, vp, vp, vp]
+        lib.dpg_shard_records.restype = ctypes.c_int
+        lib.dpg_check_shard.argtypes = [vp, vp, i64, ctypes.c_int, ctypes.c_int, vp, vp]
+        lib.dpg_check_shard.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -295,6 +302,19 @@ class Context:
         """Latches the internal error if any of n device doubles is nonzero
         (the next compact then fails)."""
         self.check(self.lib.dpg_import_error(self.handle, src_ptr, n, stream), "dpg_import_error")
+
+    def shard_records(self, pid_ptr, pk_ptr, value_ptr, n, nranks, out_pid_ptr, out_pk_ptr,
+                      out_value_ptr, counts_ptr, stream):
+        """Stable split of n records by distributed.shard_of(pid, nranks) into
+        the out arrays, destination-major; counts (device int64[nranks])."""
+        st = self.lib.dpg_shard_records(self.handle, pid_ptr, pk_ptr, value_ptr, n, nranks,
+                                        out_pid_ptr, out_pk_ptr, out_value_ptr, counts_ptr, stream)
+        self.check(st, "dpg_shard_records")
+
+    def check_shard(self, pid_ptr, n, nranks, rank, n_bad_ptr, stream):
+        """Device int64 at n_bad_ptr = records whose owner is not `rank`."""
+        st = self.lib.dpg_check_shard(self.handle, pid_ptr, n, nranks, rank, n_bad_ptr, stream)
+        self.check(st, "dpg_check_shard")
 
     def select_and_noise(self, partials: Partials, sel: SelectParams, noise: NoiseParams,
                          keep_ptr, out_ptr, stream):

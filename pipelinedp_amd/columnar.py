@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 _PID_SPAN = 1 << 32  # privacy ids of one call must span at most 2^32 values
+SHARDING_MODES = ("trusted", "verify", "shuffle")
 
 
 @dataclasses.dataclass
@@ -38,13 +39,27 @@ class ColumnarData:
     hi - lo <= 2^32; saves the device a min/max pass (out-of-range ids raise
     ValueError).  `record_id_offset`: global id of record 0 -- the record
     sampler is keyed by (pid, pk, record id), so the shards of one dataset,
-    each given its offset, sample exactly like the whole."""
+    each given its offset, sample exactly like the whole.
+
+    `sharding` (several ranks only; see pipelinedp_amd.distributed): how this
+    rank's records relate to the privacy-id shards.  "trusted": the caller
+    put every privacy id on rank distributed.shard_of(pid, R), unchecked;
+    "verify": the same claim, checked on the device (every rank raises
+    ValueError if any rank holds a record it does not own); "shuffle": the
+    records are split any way at all and are exchanged before bounding
+    (record_id_offset is then ignored; a privacy_id_range must be global).
+    "verify" and "shuffle" need integer privacy ids."""
     pid: Any = None
     pk: Any = None
     value: Any = None
     n_partitions: Optional[int] = None
     privacy_id_range: Optional[Tuple[int, int]] = None
     record_id_offset: int = 0
+    sharding: str = "trusted"
+
+    def __post_init__(self):
+        if self.sharding not in SHARDING_MODES:
+            raise ValueError(f"sharding must be one of {SHARDING_MODES}, got {self.sharding!r}")
 
     def __getitem__(self, name):
         return getattr(self, name)
@@ -70,6 +85,10 @@ class EncodedInput:
     pid_count: int = 0        # 0: unknown (the device reduces min / max)
     rec_id_offset: int = 0
     partitions_declared: bool = False  # dense ids in [0, n_partitions) given by the caller
+    # the privacy ids are the caller's integers, not a per-call dictionary
+    # encoding (which differs from rank to rank): shard_of(pid) is global
+    pid_unencoded: bool = False
+    pid_range_declared: bool = False  # pid_min / pid_count come from privacy_id_range
 
 
 def _extract(col, extractor):
@@ -274,11 +293,13 @@ def encode(col, extractors, device: torch.device, need_values: bool,
     # when known (else the device reduces it)
     pid_ids = None
     pid_min, pid_count = 0, 0
+    pid_unencoded = False
     if need_pid:
         if pid is None:
             raise ValueError("privacy_id_extractor must be set")
         if _integer_like(pid):
             pid_t = _to_tensor(pid, device).to(torch.int64)
+            pid_unencoded = True
             if pid_range is not None:
                 lo, hi = int(pid_range[0]), int(pid_range[1])
                 if not 0 < hi - lo <= _PID_SPAN:
@@ -289,6 +310,7 @@ def encode(col, extractors, device: torch.device, need_values: bool,
                 if hi - lo >= _PID_SPAN:
                     pid_t, uniq, _ = _encode_keys(pid_t, device)
                     pid_min, pid_count = 0, max(1, len(uniq))
+                    pid_unencoded = False
                 else:
                     pid_min, pid_count = lo, hi - lo + 1
             pid_ids = pid_t
@@ -303,7 +325,9 @@ def encode(col, extractors, device: torch.device, need_values: bool,
     enc = EncodedInput(pid=pid_ids, pk=pk_ids.contiguous(), value=val, n=n,
                        n_partitions=int(P), key_table=key_table, pid_min=pid_min,
                        pid_count=pid_count, rec_id_offset=rec_off,
-                       partitions_declared=hint is not None and key_table is None)
+                       partitions_declared=hint is not None and key_table is None,
+                       pid_unencoded=pid_unencoded,
+                       pid_range_declared=pid_unencoded and pid_range is not None)
     if pub_range is not None:
         enc.public_mask, enc.public_count = _range_bitmap(*pub_range, int(P), device)
     elif pub_dense is not None:

@@ -69,6 +69,7 @@ static hipError_t set_func_attr(const void *kern, hipFuncAttribute attr, int val
 #include "dpg_hist.h"
 #include "dpg_partition.h"
 #include "dpg_select.h"
+#include "dpg_shard.h"
 #include "dpg_sortb.h"
 #include "dpg_sortmw.h"
 #include "dpg_team.h"
@@ -2712,6 +2713,79 @@ int dpg_import_error(dpg_ctx *ctx, const double *src, int64_t n, void *stream) {
     if (!err) return st;
     if (n > 0) {
         k_import_error<<<1, 64, 0, s>>>(src, n, err);
+        LAUNCH_CHECK();
+    }
+    return st;
+}
+
+int dpg_shard_records(dpg_ctx *ctx, const int64_t *pid, const int64_t *pk, const double *value,
+                      int64_t n, int nranks, int64_t *out_pid, int64_t *out_pk,
+                      double *out_value, int64_t *counts, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (nranks < 1 || nranks > DPG_SHARD_MAX_RANKS)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "nranks must be in [1, DPG_SHARD_MAX_RANKS]");
+    if (n < 0 || !counts) return fail(ctx, DPG_ERR_INVALID_ARG, "n < 0 or counts is NULL");
+    if (n >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n must be < 2^31 per device");
+    // n == 0 reads and writes no record: the record pointers may be anything
+    if (n > 0 && (!pid || !pk || !out_pid || !out_pk))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "pid, pk, out_pid and out_pk must be given");
+    if (n > 0 && (value == nullptr) != (out_value == nullptr))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "value and out_value must both be given or both NULL");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int st = DPG_OK;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(counts, 0, (size_t)nranks * 8, s));
+        return st;
+    }
+    const uint32_t R = (uint32_t)nranks;
+    uint32_t bits = 0;
+    while ((1u << bits) < R) ++bits;
+    const uint32_t ntiles = (uint32_t)((n + DPG_SHARD_TILE - 1) / DPG_SHARD_TILE);
+    const uint32_t M = R * ntiles;  // <= 64 * 2^20
+    const uint32_t nchunks = (M + kScanChunk - 1) / kScanChunk;
+    WS(tiles, uint32_t, "shard.tiles", M);
+    WS(sums, uint32_t, "shard.sums", nchunks);
+    k_shard_count<<<ntiles, kShThreads, 0, s>>>(pid, (uint32_t)n, R, bits, ntiles, tiles);
+    LAUNCH_CHECK();
+    k_shard_scan_sums<<<nchunks, kShThreads, 0, s>>>(tiles, M, sums);
+    LAUNCH_CHECK();
+    k_shard_scan_top<<<1, kShThreads, 0, s>>>(sums, nchunks);
+    LAUNCH_CHECK();
+    k_shard_scan_apply<<<nchunks, kShThreads, 0, s>>>(tiles, M, sums);
+    LAUNCH_CHECK();
+    k_shard_totals<<<1, 64, 0, s>>>(tiles, (uint32_t)n, R, ntiles, counts);
+    LAUNCH_CHECK();
+    // A/B switch: DPG_SHARD_STAGE=0 stores straight from registers
+    const char *e = std::getenv("DPG_SHARD_STAGE");
+    if (e ? std::atoi(e) != 0 : true)
+        k_shard_scatter<true><<<ntiles, kShThreads, 0, s>>>(pid, pk, value, (uint32_t)n, R, bits,
+                                                            ntiles, tiles, out_pid, out_pk,
+                                                            out_value);
+    else
+        k_shard_scatter<false><<<ntiles, kShThreads, 0, s>>>(pid, pk, value, (uint32_t)n, R, bits,
+                                                             ntiles, tiles, out_pid, out_pk,
+                                                             out_value);
+    LAUNCH_CHECK();
+    return st;
+}
+
+int dpg_check_shard(dpg_ctx *ctx, const int64_t *pid, int64_t n, int nranks, int rank,
+                    int64_t *n_bad, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (nranks < 1 || nranks > DPG_SHARD_MAX_RANKS || rank < 0 || rank >= nranks)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "nranks must be in [1, DPG_SHARD_MAX_RANKS], rank in [0, nranks)");
+    if (n < 0 || !n_bad || (n > 0 && !pid))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "n < 0, or pid or n_bad is NULL");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int st = DPG_OK;
+    HIP_TRY(hipMemsetAsync(n_bad, 0, 8, s));
+    if (n > 0) {
+        const unsigned blocks = (unsigned)std::min<int64_t>((n + kShThreads - 1) / kShThreads,
+                                                            (int64_t)ctx->n_cu * 8);
+        k_check_shard<<<blocks, kShThreads, 0, s>>>(pid, n, (uint32_t)nranks, (uint32_t)rank,
+                                                    reinterpret_cast<unsigned long long *>(n_bad));
         LAUNCH_CHECK();
     }
     return st;

@@ -231,6 +231,41 @@ class DeviceAggregation:
                 self.nonce, nnz_bound, self.backend.process_group, self.backend.device)
         return self.nonce, nnz_bound
 
+    def _place_records(self, enc) -> None:
+        """ColumnarData(sharding=...) with several ranks: 'verify' checks that
+        this rank owns every privacy id it holds (one kernel, one all_reduce;
+        every rank raises when any rank fails), 'shuffle' sends every record
+        to its owner (distributed.shuffle_records) and bounds what arrives."""
+        backend = self.backend
+        mode = self.col.sharding if isinstance(self.col, columnar.ColumnarData) else "trusted"
+        if backend.world_size <= 1 or mode == "trusted" or self.bounds_already_enforced:
+            return
+        if not enc.pid_unencoded:
+            # the column's type is the same on every rank, so every rank raises
+            raise ValueError(
+                f"sharding={mode!r} needs integer privacy ids spanning at most 2^32 values: a "
+                f"per-rank dictionary encoding of other ids is not consistent across ranks")
+        dev, group = backend.device, backend.process_group
+        with torch.cuda.device(dev):
+            sptr = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            if mode == "verify":
+                n_bad = torch.empty(1, dtype=torch.int64, device=dev)
+                backend.ctx.check_shard(_ptr(enc.pid), enc.n, backend.world_size,
+                                        torch.distributed.get_rank(group), n_bad.data_ptr(), sptr)
+                # no rank raises before the collective
+                total = distributed.sum_over_ranks(n_bad, group)
+                if total:
+                    raise ValueError(
+                        f"sharding='verify': {total} records are on a rank that does not own "
+                        f"their privacy id (distributed.shard_of); use sharding='shuffle'")
+                return
+            enc.pid, enc.pk, enc.value = distributed.shuffle_records(
+                enc.pid, enc.pk, enc.value, group, backend.ctx, sptr)
+        enc.n = int(enc.pk.numel())
+        enc.rec_id_offset = 0
+        if not enc.pid_range_declared:  # a declared range is global; else the device reduces it
+            enc.pid_min, enc.pid_count = 0, 0
+
     def _run(self, gather: bool) -> DeviceResult:
         if _DROPPED:
             check_dropped()
@@ -256,6 +291,7 @@ class DeviceAggregation:
             raise ValueError(
                 "multi-GPU aggregation needs globally dense integer partition ids: "
                 "pass ColumnarData(..., n_partitions=P) with pk in [0, P) on every rank")
+        self._place_records(enc)
         bfields = self._bound_fields(P)
         l0 = (bfields["max_contributions"] if bfields["mode"] == combiners.MODE_PER_PID
               else bfields["max_partitions_contributed"])

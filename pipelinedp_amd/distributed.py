@@ -1,8 +1,37 @@
 """Multi-GPU exchange of the per-partition partials (one process per GPU).
 
-Records are sharded by privacy id before they reach a rank (each privacy id
-lives on exactly one GPU), so contribution bounding is shard-local and the
-only exchange is the merge of the per-partition partials.
+Contribution bounding is shard-local: it is correct only if each privacy id
+lives on exactly one rank, the rank `shard_of(pid, R)`.  Three ways to get
+there (`ColumnarData(sharding=...)`):
+
+* "trusted" (default) -- the caller sharded the records that way; nothing is
+  checked and no collective is added.  Records split any other way (by file,
+  by time, round-robin) release up to R x max_partitions_contributed
+  partitions per privacy id, unreported.
+* "verify" -- the same claim, checked: one kernel counts the records a rank
+  holds but does not own (dpg_check_shard), ONE all_reduce sums the counts,
+  and every rank raises ValueError when the sum is nonzero.
+* "shuffle" -- any split: `shuffle_records` orders each rank's records by
+  owner on the device (dpg_shard_records: a stable multi-way split) and ONE
+  all_to_all per column delivers them, as the reference's framework shuffle
+  groups each privacy id's records before sampling
+  (contribution_bounders.py:86-92).  Bounding then runs on the received
+  records with record id offset 0.
+
+What a shuffled release guarantees.  Pair sampling is keyed by (seed, pid, pk)
+only and each privacy id's pairs are all on one rank, so `rows`, the selected
+partition set and -- in the cross-and-per-partition and cross-partition modes,
+where a pair counts min(len, max_contributions_per_partition) -- `count` equal
+the one-process release of the whole dataset under the same seed and nonce.
+The record sampler is keyed by record id, which after a shuffle is the
+record's position in the received buffer (source rank order, input order
+within a source: deterministic): which records of an over-full pair are kept
+is still uniform and the release is correctly bounded, but `sum` in every
+mode and `count` under `max_contributions` may differ from the one-process
+release; they equal the release of each rank's received records.
+
+With the records in place the only further exchange is the merge of the
+per-partition partials.
 
 Ownership is by partition key: rank r owns partitions r, r + R, r + 2R, ...
 (R ranks; `pk mod R`, the identity hash of the dense ids), at local index
@@ -94,6 +123,91 @@ def release_header(nonce: int, nnz_bound: int, group, device) -> Tuple[int, int]
     dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
     got = t.tolist()
     return got[0] & ((1 << 64) - 1), got[1]
+
+
+def sum_over_ranks(x: torch.Tensor, group) -> int:
+    """ONE all_reduce (sum) of a one-element int64 tensor; the total on every
+    rank (sharding='verify': the mis-sharded records of all ranks)."""
+    t = x.to(_coll_device(group, x.device)).reshape(1).clone()
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return int(t.item())
+
+
+def _exchange_column(send: torch.Tensor, in_splits, out_splits, group) -> torch.Tensor:
+    """One all_to_all_single of a destination-major column with uneven
+    splits (on gloo staged through host memory)."""
+    dev = send.device
+    if _is_nccl(group):
+        recv = torch.empty(sum(out_splits), dtype=send.dtype, device=dev)
+        dist.all_to_all_single(recv, send, out_splits, in_splits, group=group)
+        return recv
+    recv = torch.empty(sum(out_splits), dtype=send.dtype, device="cpu")
+    dist.all_to_all_single(recv, send.cpu(), out_splits, in_splits, group=group)
+    return recv.to(dev)
+
+
+def shuffle_records(pid: torch.Tensor, pk: torch.Tensor, value: Optional[torch.Tensor], group,
+                    ctx=None, stream=None):
+    """Delivers every record to the rank `shard_of(pid, R)`; returns this
+    rank's (pid, pk, value) in source-rank order, input order within a source
+    (value None stays None: every rank must pass None or none of them).
+
+    Device tensors with the library context `ctx`: the send order is ONE
+    stable split on the device (dpg_shard_records, stream-ordered on `stream`,
+    torch's current stream); reading its R counts back is the shuffle's one
+    host synchronisation -- the receive sizes must be known.  Host tensors
+    (the gloo CPU tests, no context): the same layout from a stable argsort
+    of shard_of and a bincount.
+
+    Every rank runs the same collectives whatever its local n: one all_gather
+    of the R counts (every rank then holds the R x R matrix, so its own send
+    and receive splits, and sees a receive total of 2^31 or more on any rank:
+    all ranks then raise the same ValueError), and one all_to_all_single per
+    column.  The send buffers are freed column by column."""
+    world = dist.get_world_size(group)
+    rank = dist.get_rank(group)
+    dev = pid.device
+    n = pid.numel()
+    pid = pid.to(torch.int64).contiguous()
+    pk = pk.to(torch.int64).contiguous()
+    if value is not None:
+        value = value.to(torch.float64).contiguous()
+    if ctx is not None and dev.type == "cuda":
+        s_pid, s_pk = torch.empty_like(pid), torch.empty_like(pk)
+        s_val = torch.empty_like(value) if value is not None else None
+        counts = torch.empty(world, dtype=torch.int64, device=dev)
+        ctx.shard_records(pid.data_ptr(), pk.data_ptr(),
+                          value.data_ptr() if value is not None else None, n, world,
+                          s_pid.data_ptr(), s_pk.data_ptr(),
+                          s_val.data_ptr() if s_val is not None else None,
+                          counts.data_ptr(), stream)
+        counts = counts.cpu()  # the one host synchronisation
+    else:
+        dest = shard_of(pid, world)
+        order = torch.argsort(dest, stable=True)
+        counts = torch.bincount(dest, minlength=world).cpu()
+        s_pid, s_pk = pid[order], pk[order]
+        s_val = value[order] if value is not None else None
+    del pid, pk, value
+    cdev = _coll_device(group, dev)
+    rows = [torch.empty(world, dtype=torch.int64, device=cdev) for _ in range(world)]
+    dist.all_gather(rows, counts.to(cdev), group=group)
+    matrix = torch.stack(rows).cpu()  # [source, destination]
+    worst = int(matrix.sum(0).max().item())
+    if worst >= 1 << 31:
+        raise ValueError(f"record shuffle: one rank would receive {worst} records; a rank "
+                         f"holds fewer than 2^31")
+    in_splits = matrix[rank].tolist()
+    out_splits = matrix[:, rank].tolist()
+    r_pid = _exchange_column(s_pid, in_splits, out_splits, group)
+    del s_pid
+    r_pk = _exchange_column(s_pk, in_splits, out_splits, group)
+    del s_pk
+    r_val = None
+    if s_val is not None:
+        r_val = _exchange_column(s_val, in_splits, out_splits, group)
+        del s_val
+    return r_pid, r_pk, r_val
 
 
 def _names(tensors) -> list:
