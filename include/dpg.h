@@ -35,6 +35,11 @@
  *        (compute_dataset_histograms_on_preaggregated_data), which feed
  *        DPEngine.calculate_private_contribution_bounds (dp_engine.py:432-484)
  *        and analysis/parameter_tuning.py:278-348 (tune).
+ *   dpg_bound_records / dpg_quantile_keys / dpg_quantiles <- QuantileCombiner
+ *        (pipeline_dp/combiners.py:532-611: PyDP QuantileTree per
+ *        (privacy id, partition) accumulator, merged per partition, then
+ *        compute_quantiles) on the records contribution bounding keeps
+ *        (contribution_bounders.py:66-105).
  */
 #ifndef DPG_H_
 #define DPG_H_
@@ -97,6 +102,9 @@ extern "C" {
 #define DPG_SLOT_SUM 1 /* SUM, or the normalised sum of MEAN/VARIANCE */
 #define DPG_SLOT_NSQ 2 /* normalised sum of squares (VARIANCE)        */
 #define DPG_SLOT_PID 3 /* PRIVACY_ID_COUNT                             */
+/* quantile tree: node nu of a partition draws from slot DPG_SLOT_QNODE0 + nu
+ * (root = node 0, children of node i = 16 i + 1 .. 16 i + 16) */
+#define DPG_SLOT_QNODE0 16
 
 /* value-vector entries an output column can be mapped from */
 #define DPG_V_COUNT 0
@@ -437,8 +445,71 @@ int dpg_shard_records(dpg_ctx *ctx, const int64_t *pid, const int64_t *pk, const
 int dpg_check_shard(dpg_ctx *ctx, const int64_t *pid, int64_t n, int nranks, int rank,
                     int64_t *n_bad, void *stream);
 
+/* ---- percentiles: kept records, quantile tree (combiners.py:532-611) ----
+ * Stable LSD radix sort of n (key, payload) pairs by the key bits
+ * [begin_bit, end_bit) (0 <= begin_bit <= end_bit <= 64), 8 bits per pass;
+ * a pass whose digit takes one value over the whole input is skipped on the
+ * device.  Device arrays of n entries; vals_in / vals_out may both be NULL
+ * (keys only).  The outputs must not overlap the inputs.  n < 2^31 (else
+ * DPG_ERR_UNSUPPORTED); n == 0 is a no-op.  Stream-ordered, no host
+ * synchronisation (csrc/dpg_rsort.h). */
+int dpg_sort_pairs_u64(dpg_ctx *ctx, const uint64_t *keys_in, const uint32_t *vals_in, int64_t n,
+                       int32_t begin_bit, int32_t end_bit, uint64_t *keys_out, uint32_t *vals_out,
+                       void *stream);
+
+/* keep[i] (device uint8[n]) = 1 iff record i is in the kept set of
+ * dpg_bound_aggregate under the same context seed and params (nonce,
+ * rec_id_offset, public_mask, pid_min / pid_count, mode, mpc, mcpp): pairs of
+ * a privacy id ascending by (pair priority << 32 | pk), the first mpc kept;
+ * records of a pair ascending by the 64-bit record priority, the first mcpp
+ * kept (DPG_MODE_CROSS_PARTITION: all of them).  DPG_MODE_PER_PRIVACY_ID is
+ * DPG_ERR_UNSUPPORTED, as is n >= 2^31.  A privacy id outside a declared
+ * range or a pk outside [0, P) is never kept and sets bit 0 of the
+ * context's device error word, which dpg_compact_kept_async copies to
+ * info[1] (the call itself cannot report it: it does not wait for the
+ * device).  pid_count == 0 needs no range reduction here: ids are compared
+ * as 64-bit values.  Stream-ordered, no host synchronisation
+ * (csrc/dpg_records.h). */
+int dpg_bound_records(dpg_ctx *ctx, const int64_t *pid, const int64_t *pk, int64_t n,
+                      const dpg_bound_params *params, uint8_t *keep, void *stream);
+
+typedef struct dpg_quantile_params {
+    double lo, hi;        /* the tree covers [lo, hi]: min_value, max_value  */
+    int32_t noise_kind;   /* DPG_NOISE_*                                     */
+    int32_t n_quantiles;  /* 1..16                                           */
+    double scale;         /* b or sigma of every node count                  */
+    double quantiles[16]; /* in [0, 1]                                       */
+    int64_t pk_offset;    /* global pk of local partition i is               */
+    int64_t pk_stride;    /*   pk_offset + i * pk_stride; <= 0 means 1       */
+    uint64_t nonce;       /* per-release nonce (see dpg_bound_params)        */
+} dpg_quantile_params;
+
+/* Tree keys: keys[0, *n_keys) (device uint64[n], device int64) receive
+ * pk << 16 | leaf of every record with keep[i] != 0 and a non-NaN value,
+ * sorted; leaf = min(65535, floor((clamp(v, lo, hi) - lo) * 65536 / (hi - lo)))
+ * (0 when lo == hi).  pk in [0, P), P < 2^32 - 1; n < 2^31.  Stream-ordered,
+ * no host synchronisation. */
+int dpg_quantile_keys(dpg_ctx *ctx, const int64_t *pk, const double *value, const uint8_t *keep,
+                      int64_t n, int64_t n_partitions, const dpg_quantile_params *qparams,
+                      uint64_t *keys, int64_t *n_keys, void *stream);
+
+/* out[k][j] (device double[P][n_quantiles]) = the quantiles[j]-quantile of
+ * partition k from its noised 16-ary tree of height 4 (Google's walk:
+ * children below 0.0075 of their siblings' clamped total are dropped, the
+ * first child whose inclusive share reaches rank - 1e-6 is entered, the
+ * result interpolates over the last node's range).  The noised count of
+ * node nu is add_noise(kind, count, scale, stream seed, global pk,
+ * DPG_SLOT_QNODE0 + nu): a pure function of (seed, nonce, partition, node).
+ * Rows of partitions with keep_partition[k] == 0 (device uint8[P], or NULL:
+ * all) are left untouched.  keys / n_keys as dpg_quantile_keys wrote them
+ * (csrc/dpg_quantile.h). */
+int dpg_quantiles(dpg_ctx *ctx, const uint64_t *keys, const int64_t *n_keys, int64_t n_partitions,
+                  const dpg_quantile_params *qparams, const uint8_t *keep_partition, double *out,
+                  void *stream);
+
 /* Timing/profiling aid: per-stage device time (ms) of the last
- * dpg_bound_aggregate / dpg_preaggregate / dpg_dataset_histograms call,
+ * dpg_bound_aggregate / dpg_preaggregate / dpg_dataset_histograms /
+ * dpg_bound_records / dpg_quantile_keys call,
  * measured with HIP events on its stream (waits for the last event).
  * names (comma separated, <= names_len bytes): e.g. "begin",
  * "partition1:hist", "partition1:scatter", "partition2:hist",

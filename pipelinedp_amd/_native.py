@@ -22,12 +22,16 @@ EXPORTED = ("dpg_ctx_create", "dpg_ctx_destroy", "dpg_last_error", "dpg_set_seed
             "dpg_utility_analysis", "dpg_dataset_histograms",
             "dpg_comm_unique_id", "dpg_ctx_create_comm", "dpg_reduce_scatter_partials",
             "dpg_pack_partials", "dpg_unpack_partials", "dpg_export_error",
-            "dpg_import_error", "dpg_shard_records", "dpg_check_shard")
+            "dpg_import_error", "dpg_shard_records", "dpg_check_shard",
+            "dpg_sort_pairs_u64", "dpg_bound_records", "dpg_quantile_keys", "dpg_quantiles")
 
 COMM_ID_BYTES = 128  # DPG_COMM_ID_BYTES
 
 SHARD_MAX_RANKS = 64  # DPG_SHARD_MAX_RANKS
 SHARD_TILE = 2048  # DPG_SHARD_TILE (csrc/dpg_shard.h): records per workgroup of the split
+
+SLOT_QNODE0 = 16  # DPG_SLOT_QNODE0: noise slot of quantile-tree node 0
+QUANTILE_MAX = 16  # quantiles per dpg_quantiles call
 
 HIST_INT_BINS = 16300  # DPG_HIST_INT_BINS
 HIST_SUM_BINS = 10000  # DPG_HIST_SUM_BINS
@@ -71,6 +75,15 @@ class NoiseParams(ctypes.Structure):
                 ("msq_const_value", ctypes.c_double)]
 
 
+class QuantileParams(ctypes.Structure):
+    """dpg_quantile_params: the tree's range, node noise and quantiles."""
+    _fields_ = [("lo", ctypes.c_double), ("hi", ctypes.c_double),
+                ("noise_kind", ctypes.c_int32), ("n_quantiles", ctypes.c_int32),
+                ("scale", ctypes.c_double), ("quantiles", ctypes.c_double * 16),
+                ("pk_offset", ctypes.c_int64), ("pk_stride", ctypes.c_int64),
+                ("nonce", ctypes.c_uint64)]
+
+
 class PairEntry(ctypes.Structure):
     """dpg_pair_entry: one (privacy id, partition) pair of the pre-aggregate."""
     _fields_ = [("pk", ctypes.c_uint32), ("count", ctypes.c_uint32), ("sum", ctypes.c_double),
@@ -106,7 +119,7 @@ class UaParams(ctypes.Structure):
 def fill(struct_type, fields: dict):
     s = struct_type()
     for k, v in fields.items():
-        if k in ("out_src", "scale"):
+        if k in ("out_src", "quantiles") or (k == "scale" and not isinstance(v, float)):
             arr = getattr(s, k)
             for i, x in enumerate(v):
                 arr[i] = x
@@ -206,6 +219,15 @@ def load():
         lib.dpg_shard_records.restype = ctypes.c_int
         lib.dpg_check_shard.argtypes = [vp, vp, i64, ctypes.c_int, ctypes.c_int, vp, vp]
         lib.dpg_check_shard.restype = ctypes.c_int
+        lib.dpg_sort_pairs_u64.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
+        lib.dpg_sort_pairs_u64.restype = ctypes.c_int
+        lib.dpg_bound_records.argtypes = [vp, vp, vp, i64, ctypes.POINTER(BoundParams), vp, vp]
+        lib.dpg_bound_records.restype = ctypes.c_int
+        lib.dpg_quantile_keys.argtypes = [vp, vp, vp, vp, i64, i64,
+                                          ctypes.POINTER(QuantileParams), vp, vp, vp]
+        lib.dpg_quantile_keys.restype = ctypes.c_int
+        lib.dpg_quantiles.argtypes = [vp, vp, vp, i64, ctypes.POINTER(QuantileParams), vp, vp, vp]
+        lib.dpg_quantiles.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -315,6 +337,35 @@ class Context:
         """Device int64 at n_bad_ptr = records whose owner is not `rank`."""
         st = self.lib.dpg_check_shard(self.handle, pid_ptr, n, nranks, rank, n_bad_ptr, stream)
         self.check(st, "dpg_check_shard")
+
+    def sort_pairs_u64(self, keys_in_ptr, vals_in_ptr, n, begin_bit, end_bit, keys_out_ptr,
+                       vals_out_ptr, stream):
+        """Stable radix sort of n (uint64 key, uint32 payload) pairs by the key
+        bits [begin_bit, end_bit); the payload pointers may both be None."""
+        st = self.lib.dpg_sort_pairs_u64(self.handle, keys_in_ptr, vals_in_ptr, n, begin_bit,
+                                         end_bit, keys_out_ptr, vals_out_ptr, stream)
+        self.check(st, "dpg_sort_pairs_u64")
+
+    def bound_records(self, pid_ptr, pk_ptr, n, bound: BoundParams, keep_ptr, stream):
+        """Device uint8[n] at keep_ptr: 1 for the records dpg_bound_aggregate
+        keeps under the same seed and params."""
+        st = self.lib.dpg_bound_records(self.handle, pid_ptr, pk_ptr, n, ctypes.byref(bound),
+                                        keep_ptr, stream)
+        self.check(st, "dpg_bound_records")
+
+    def quantile_keys(self, pk_ptr, value_ptr, keep_ptr, n, n_partitions, q: QuantileParams,
+                      keys_ptr, n_keys_ptr, stream):
+        """Sorted tree keys (pk << 16 | leaf) of the kept, non-NaN records."""
+        st = self.lib.dpg_quantile_keys(self.handle, pk_ptr, value_ptr, keep_ptr, n, n_partitions,
+                                        ctypes.byref(q), keys_ptr, n_keys_ptr, stream)
+        self.check(st, "dpg_quantile_keys")
+
+    def quantiles(self, keys_ptr, n_keys_ptr, n_partitions, q: QuantileParams,
+                  keep_partition_ptr, out_ptr, stream):
+        """Device double[P][n_quantiles] at out_ptr from the noised trees."""
+        st = self.lib.dpg_quantiles(self.handle, keys_ptr, n_keys_ptr, n_partitions,
+                                    ctypes.byref(q), keep_partition_ptr, out_ptr, stream)
+        self.check(st, "dpg_quantiles")
 
     def select_and_noise(self, partials: Partials, sel: SelectParams, noise: NoiseParams,
                          keep_ptr, out_ptr, stream):

@@ -30,6 +30,17 @@ NOISE_NONE, NOISE_LAPLACE, NOISE_GAUSSIAN = 0, 1, 2
 _FIELD_SOURCE = {"count": V_COUNT, "sum": V_SUM, "mean": V_MEAN,
                  "variance": V_VARIANCE, "privacy_id_count": V_PID}
 
+QUANTILE_TREE_HEIGHT = 4  # csrc/dpg_quantile.h: 16-ary, 65536 leaves
+QUANTILE_MAX = 16         # dpg_quantile_params.quantiles
+
+
+def percentile_field(p) -> str:
+    """combiners.py:577-587: percentile_90, percentile_90_5."""
+    if int(p) == p:
+        return f"percentile_{int(p)}"
+    return "percentile_" + str(p).replace(".", "_")
+
+
 _named_tuples: Dict[Tuple[str, ...], type] = {}
 
 
@@ -49,8 +60,7 @@ class CompoundPlan:
                  accountant: budget_accounting.BudgetAccountant):
         self.params = params
         metrics = set(params.metrics or [])
-        unsupported = [m for m in metrics
-                       if m == agg.Metrics.VECTOR_SUM or m.is_percentile]
+        unsupported = [m for m in metrics if m == agg.Metrics.VECTOR_SUM]
         if unsupported:
             raise NotImplementedError(
                 f"{unsupported} are not supported by the MI355X backend "
@@ -97,6 +107,19 @@ class CompoundPlan:
             fields.append("privacy_id_count")
             self.mask |= M_PID
             self._pid_sens = dpc.sensitivities_for_privacy_id_count(params)
+        # combiners.py:839-856: one QuantileCombiner for every percentile, one
+        # budget request, fields in the order of params.metrics
+        self.percentiles: List[float] = [m.parameter for m in (params.metrics or [])
+                                         if m.is_percentile]
+        if self.percentiles:
+            if len(self.percentiles) > QUANTILE_MAX:
+                raise NotImplementedError(
+                    f"at most {QUANTILE_MAX} percentiles per aggregation are supported")
+            if params.min_value is None or params.max_value is None:
+                raise ValueError("percentiles need min_value and max_value")
+            self.specs["percentile"] = accountant.request_budget(mech, weight=w)
+            fields += [percentile_field(p) for p in self.percentiles]
+        self.n_noise_outputs = len(fields) - len(self.percentiles)
         self.fields = tuple(fields)
         self.MetricsTuple = metrics_tuple_type(self.fields)
         self._mechanisms = None
@@ -104,6 +127,8 @@ class CompoundPlan:
     # ------------------------------------------------------------ bounding
     def expects_per_partition_sampling(self) -> bool:
         """combiners.py:76-85, 323-324, 364-365, 738-739."""
+        if self.percentiles:
+            return True
         if self.family != FAMILY_SCALAR or "count" in self.specs:
             return True
         if "sum" in self.specs:
@@ -126,7 +151,7 @@ class CompoundPlan:
         return SUM_CLIP_VALUE
 
     def needs_values(self) -> bool:
-        return bool(self.mask & (M_SUM | M_MEAN | M_VARIANCE))
+        return bool(self.mask & (M_SUM | M_MEAN | M_VARIANCE)) or bool(self.percentiles)
 
     def bound_fields(self, n_partitions: int) -> dict:
         """Field values of dpg_bound_params."""
@@ -222,10 +247,32 @@ class CompoundPlan:
         if "privacy_id_count" in self.specs:
             scale[SLOT_PID] = self.mechanisms()["privacy_id_count"].scale
             slot_mask |= 1 << SLOT_PID
-        out_src = [_FIELD_SOURCE[f] for f in self.fields] + [0] * (8 - len(self.fields))
+        own = self.fields[:self.n_noise_outputs]  # the percentile columns are not its
+        out_src = [_FIELD_SOURCE[f] for f in own] + [0] * (8 - len(own))
         return dict(noise_kind=kind if with_noise else NOISE_NONE, family=self.family,
-                    slot_mask=slot_mask, n_outputs=len(self.fields), out_src=out_src,
+                    slot_mask=slot_mask, n_outputs=len(own), out_src=out_src,
                     scale=scale, **extra)
+
+    def quantile_mechanism(self) -> dpc.AdditiveMechanism:
+        """The one mechanism of every tree node (combiners.py:589-606: a
+        privacy id touches max_partitions_contributed trees, one node per
+        level in each, max_contributions_per_partition times)."""
+        p = self.params
+        spec = self.specs["percentile"]
+        sens = dpc.Sensitivities(l0=p.max_partitions_contributed * QUANTILE_TREE_HEIGHT,
+                                 linf=p.max_contributions_per_partition)
+        return dpc.AdditiveMechanism(self.noise_kind, spec.eps, spec.delta, sens)
+
+    def quantile_fields(self, with_noise: bool = True) -> dict:
+        """Field values of dpg_quantile_params but the partition offset,
+        stride and nonce (after compute_budgets())."""
+        kind = {agg.NoiseKind.LAPLACE: NOISE_LAPLACE,
+                agg.NoiseKind.GAUSSIAN: NOISE_GAUSSIAN}[self.noise_kind]
+        return dict(lo=float(self.params.min_value), hi=float(self.params.max_value),
+                    noise_kind=kind if with_noise else NOISE_NONE,
+                    n_quantiles=len(self.percentiles),
+                    scale=float(self.quantile_mechanism().scale),
+                    quantiles=[p / 100.0 for p in self.percentiles])
 
     # ------------------------------------------------------------ report
     def explain_computation(self) -> List:
@@ -233,7 +280,7 @@ class CompoundPlan:
         if self.family == FAMILY_VARIANCE:
             spec = self.specs["variance"]
             stages.append(lambda: f"Computed variance with (eps={spec.eps} delta={spec.delta})")
-            return stages + self._pid_explain()
+            return stages + self._pid_explain() + self._percentile_explain()
         if self.family == FAMILY_MEAN:
             mid = dpc.compute_middle(self.params.min_value, self.params.max_value)
 
@@ -244,13 +291,21 @@ class CompoundPlan:
                         f"    b. Applied to 'count' {m['count'].describe()}\n"
                         f"    c. Applied to 'normalized_sum' {m['normalized_sum'].describe()}")
             stages.append(mean_report)
-            return stages + self._pid_explain()
+            return stages + self._pid_explain() + self._percentile_explain()
         for name in ("count", "sum"):
             if name in self.specs:
                 stages.append(lambda name=name: (
                     f"Computed DP {name} with\n     "
                     f"{self.mechanisms()[name].describe()}"))
-        return stages + self._pid_explain()
+        return stages + self._pid_explain() + self._percentile_explain()
+
+    def _percentile_explain(self) -> List:
+        """combiners.py:608-611."""
+        if not self.percentiles:
+            return []
+        spec = self.specs["percentile"]
+        return [lambda: (f"Computed percentiles {self.percentiles} with "
+                         f"(eps={spec.eps} delta={spec.delta})")]
 
     def _pid_explain(self) -> List:
         if "privacy_id_count" not in self.specs:

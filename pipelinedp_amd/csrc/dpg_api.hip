@@ -68,6 +68,9 @@ static hipError_t set_func_attr(const void *kern, hipFuncAttribute attr, int val
 #include "dpg_common.h"
 #include "dpg_hist.h"
 #include "dpg_partition.h"
+#include "dpg_quantile.h"
+#include "dpg_records.h"
+#include "dpg_rsort.h"
 #include "dpg_select.h"
 #include "dpg_shard.h"
 #include "dpg_sortb.h"
@@ -2789,6 +2792,258 @@ int dpg_check_shard(dpg_ctx *ctx, const int64_t *pid, int64_t n, int nranks, int
         LAUNCH_CHECK();
     }
     return st;
+}
+
+// ---- percentiles: radix sort, kept records, quantile tree
+
+// The sort of dpg_rsort.h over key bits [begin_bit, end_bit): b.ktmp / b.vtmp
+// are taken from the workspace.  n_dev: the record count on the device
+// (<= n_max, which sizes the launches), or NULL.  tag: stage names for
+// dpg_last_stage_times, or NULL.
+static int rsort_run(dpg_ctx *ctx, hipStream_t s, RsBufs b, uint32_t n_max, const int64_t *n_dev,
+                     uint32_t begin_bit, uint32_t end_bit, const char *tag) {
+    int st = DPG_OK;
+    if (n_max == 0) return st;
+    const uint32_t npass = (end_bit - begin_bit + 7u) / 8u;  // <= kRsMaxPasses
+    const uint32_t ntiles = (n_max + DPG_SHARD_TILE - 1) / DPG_SHARD_TILE;
+    const uint32_t M = kRsDigits * ntiles;  // <= 2^8 * 2^20
+    const uint32_t nchunks = (M + kScanChunk - 1) / kScanChunk;
+    WS(hist, uint32_t, "rsort.hist", kRsMaxPasses * kRsDigits);
+    WS(plan, RsPlan, "rsort.plan", 1);
+    WS(tiles, uint32_t, "rsort.tiles", M);
+    WS(sums, uint32_t, "rsort.sums", nchunks);
+    WS(ktmp, uint64_t, "rsort.ktmp", n_max);
+    b.ktmp = ktmp;
+    b.vtmp = nullptr;
+    if (b.vin) {
+        WS(vtmp, uint32_t, "rsort.vtmp", n_max);
+        b.vtmp = vtmp;
+    }
+    const unsigned blocks = (unsigned)std::min<int64_t>(((int64_t)n_max + kShThreads - 1) / kShThreads,
+                                                        (int64_t)ctx->n_cu * 8);
+    if (tag) stage(ctx, s, std::string(tag) + ":hist");
+    HIP_TRY(hipMemsetAsync(hist, 0, sizeof(uint32_t) * kRsMaxPasses * kRsDigits, s));
+    if (npass) {
+        k_rs_hist<<<blocks, kShThreads, 0, s>>>(b.kin, n_max, n_dev, begin_bit, end_bit, npass, hist);
+        LAUNCH_CHECK();
+    }
+    k_rs_plan<<<1, kRsDigits, 0, s>>>(hist, n_max, n_dev, npass, plan);
+    LAUNCH_CHECK();
+    for (uint32_t p = 0; p < npass; ++p) {
+        const uint32_t shift = begin_bit + 8u * p;
+        const uint32_t mask = (1u << std::min(8u, end_bit - shift)) - 1u;
+        if (tag) stage(ctx, s, std::string(tag) + ":pass" + std::to_string(p));
+        k_rs_count<<<ntiles, kShThreads, 0, s>>>(b, n_max, n_dev, plan, p, shift, mask, ntiles, tiles);
+        LAUNCH_CHECK();
+        k_shard_scan_sums<<<nchunks, kShThreads, 0, s>>>(tiles, M, sums);
+        LAUNCH_CHECK();
+        k_shard_scan_top<<<1, kShThreads, 0, s>>>(sums, nchunks);
+        LAUNCH_CHECK();
+        k_shard_scan_apply<<<nchunks, kShThreads, 0, s>>>(tiles, M, sums);
+        LAUNCH_CHECK();
+        k_rs_scatter<<<ntiles, kShThreads, 0, s>>>(b, n_max, n_dev, plan, p, shift, mask, ntiles, tiles);
+        LAUNCH_CHECK();
+    }
+    k_rs_copy<<<blocks, kShThreads, 0, s>>>(b, n_max, n_dev, plan);
+    LAUNCH_CHECK();
+    return st;
+}
+
+static bool ranges_overlap(const void *a, const void *b, size_t bytes) {
+    const char *x = static_cast<const char *>(a), *y = static_cast<const char *>(b);
+    return x && y && x < y + bytes && y < x + bytes;
+}
+
+int dpg_sort_pairs_u64(dpg_ctx *ctx, const uint64_t *keys_in, const uint32_t *vals_in, int64_t n,
+                       int32_t begin_bit, int32_t end_bit, uint64_t *keys_out, uint32_t *vals_out,
+                       void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (n < 0 || begin_bit < 0 || end_bit > 64 || begin_bit > end_bit)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "n < 0 or bad bit range");
+    if (n >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n must be < 2^31 per device");
+    if (n == 0) return DPG_OK;
+    if (!keys_in || !keys_out) return fail(ctx, DPG_ERR_INVALID_ARG, "keys_in and keys_out must be given");
+    if ((vals_in == nullptr) != (vals_out == nullptr))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "vals_in and vals_out must both be given or both NULL");
+    if (ranges_overlap(keys_in, keys_out, (size_t)n * 8) || ranges_overlap(vals_in, vals_out, (size_t)n * 4))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "the outputs must not overlap the inputs");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    RsBufs b{keys_in, vals_in, nullptr, keys_out, nullptr, vals_out};
+    return rsort_run(ctx, static_cast<hipStream_t>(stream), b, (uint32_t)n, nullptr,
+                     (uint32_t)begin_bit, (uint32_t)end_bit, nullptr);
+}
+
+int dpg_bound_records(dpg_ctx *ctx, const int64_t *pid, const int64_t *pk, int64_t n,
+                      const dpg_bound_params *p, uint8_t *keep, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (!p || n < 0 || (n > 0 && (!pid || !pk || !keep)))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "null argument");
+    if (p->n_partitions <= 0 || p->n_partitions >= 0xFFFFFFFFll)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "n_partitions must be in [1, 2^32-1)");
+    if (p->mode < 0 || p->mode > 2) return fail(ctx, DPG_ERR_INVALID_ARG, "bad mode");
+    if (p->mode == DPG_MODE_PER_PRIVACY_ID)
+        return fail(ctx, DPG_ERR_UNSUPPORTED,
+                    "kept records of per-privacy-id (max_contributions) bounding are not built");
+    if (p->max_partitions_contributed <= 0 || p->max_contributions_per_partition <= 0)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "contribution bounds must be positive");
+    if (n >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n must be < 2^31 per device");
+    if (p->pid_count < 0 || p->pid_count > (1ll << 32))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "pid_count must be in [0, 2^32]");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int st = DPG_OK;
+    if (n == 0) return st;
+    ctx->stage_names.clear();
+    ctx->n_events_used = 0;
+    ctx->last_stream = s;
+    const uint32_t N = (uint32_t)n;
+    RecArgs a{};
+    a.pid = pid;
+    a.pk = pk;
+    a.pub = p->public_mask;
+    a.U = (uint64_t)p->pid_count;
+    a.pid_min = a.U ? (uint64_t)p->pid_min : 0ull;
+    a.P = (uint64_t)p->n_partitions;
+    a.seed = stream_seed(ctx->seed, p->nonce);
+    a.rec_id_offset = (uint64_t)p->rec_id_offset;
+    a.mpc = (uint32_t)std::min<int64_t>(p->max_partitions_contributed, 0xFFFFFFFFll);
+    a.mcpp = (uint32_t)std::min<int64_t>(p->max_contributions_per_partition, 0xFFFFFFFFll);
+    a.cross = p->mode == DPG_MODE_CROSS_PARTITION ? 1u : 0u;
+    // the error word of the context's last bounding (bit 0: key range), or a
+    // word of its own when none ran
+    uint32_t *err = const_cast<uint32_t *>(ctx->last_err);
+    if (!err) {
+        WS(w, uint32_t, "records.err", 1);
+        HIP_TRY(hipMemsetAsync(w, 0, 4, s));
+        ctx->last_err = err = w;
+    }
+    WS(k0, uint64_t, "records.k0", N);
+    WS(k1, uint64_t, "records.k1", N);
+    WS(v0, uint32_t, "records.v0", N);
+    WS(v1, uint32_t, "records.v1", N);
+    const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cu * 16);
+    // ---- records of a pair by rec_prio (the payload becomes the record index)
+    stage(ctx, s, "records:keys");
+    k_rec_key<0><<<blocks, 256, 0, s>>>(a, N, nullptr, k0, v0, err);
+    LAUNCH_CHECK();
+    uint32_t *idx = v0, *other = v1;
+    if (!a.cross) {
+        // the low word of rec_prio is the low word of the global record id:
+        // input order already, unless the ids wrap 2^32 inside this call
+        const bool wraps = (a.rec_id_offset & 0xFFFFFFFFull) + (uint64_t)N > (1ull << 32);
+        RsBufs b{k0, idx, nullptr, k1, nullptr, other};
+        st = rsort_run(ctx, s, b, N, nullptr, wraps ? 0u : 32u, 64u, "records:rec");
+        if (st) return st;
+        std::swap(idx, other);
+    }
+    // ---- pairs of a privacy id by (pair_prio << 32 | pk)
+    stage(ctx, s, "records:pairkeys");
+    k_rec_key<1><<<blocks, 256, 0, s>>>(a, N, idx, k0, nullptr, err);
+    LAUNCH_CHECK();
+    {
+        RsBufs b{k0, idx, nullptr, k1, nullptr, other};
+        st = rsort_run(ctx, s, b, N, nullptr, 0u, 64u, "records:pair");
+        if (st) return st;
+        std::swap(idx, other);
+    }
+    // ---- privacy ids together
+    stage(ctx, s, "records:pidkeys");
+    k_rec_key<2><<<blocks, 256, 0, s>>>(a, N, idx, k0, nullptr, err);
+    LAUNCH_CHECK();
+    {
+        RsBufs b{k0, idx, nullptr, k1, nullptr, other};
+        st = rsort_run(ctx, s, b, N, nullptr, 0u, a.U ? std::max<uint32_t>(1, bits_for(a.U)) : 64u,
+                       "records:pid");
+        if (st) return st;
+        std::swap(idx, other);
+    }
+    // ---- ranks from one scan over the sorted sequence
+    stage(ctx, s, "records:mark");
+    const uint32_t ntiles = (N + DPG_SHARD_TILE - 1) / DPG_SHARD_TILE;
+    WS(tsum, uint32_t, "records.tsum", ntiles);
+    WS(tord, uint32_t, "records.tord", ntiles);
+    WS(tpos, uint32_t, "records.tpos", ntiles);
+    WS(flags, uint64_t, "records.flags", (size_t)ntiles * kShThreads);
+    // the sort's keys-out buffer holds the sorted pid keys
+    k_rec_mark_count<<<ntiles, kShThreads, 0, s>>>(a, k1, idx, N, flags, tsum, tord, tpos);
+    LAUNCH_CHECK();
+    k_rec_mark_top<<<1, kShThreads, 0, s>>>(ntiles, tsum, tord, tpos);
+    LAUNCH_CHECK();
+    k_rec_mark_apply<<<ntiles, kShThreads, 0, s>>>(a, idx, N, flags, tsum, tord, tpos, keep);
+    LAUNCH_CHECK();
+    stage(ctx, s, "records:end");
+    return st;
+}
+
+static int quantile_args(dpg_ctx *ctx, const dpg_quantile_params *q, int64_t P, QtArgs *a) {
+    if (!q) return fail(ctx, DPG_ERR_INVALID_ARG, "null argument");
+    if (P <= 0 || P >= 0xFFFFFFFFll)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "n_partitions must be in [1, 2^32-1)");
+    if (q->n_quantiles < 1 || q->n_quantiles > 16)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "n_quantiles must be in [1, 16]");
+    if (!(q->lo <= q->hi)) return fail(ctx, DPG_ERR_INVALID_ARG, "lo must be <= hi");
+    if (q->noise_kind < DPG_NOISE_NONE || q->noise_kind > DPG_NOISE_GAUSSIAN)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "bad noise_kind");
+    for (int j = 0; j < q->n_quantiles; ++j)
+        if (!(q->quantiles[j] >= 0.0 && q->quantiles[j] <= 1.0))
+            return fail(ctx, DPG_ERR_INVALID_ARG, "quantiles must lie in [0, 1]");
+    a->lo = q->lo;
+    a->hi = q->hi;
+    a->noise_kind = q->noise_kind;
+    a->nq = q->n_quantiles;
+    a->scale = q->scale;
+    for (int j = 0; j < 16; ++j) a->q[j] = j < q->n_quantiles ? q->quantiles[j] : 0.0;
+    a->pk_offset = q->pk_offset;
+    a->pk_stride = q->pk_stride > 0 ? q->pk_stride : 1;
+    a->seed = stream_seed(ctx->seed, q->nonce);
+    return DPG_OK;
+}
+
+int dpg_quantile_keys(dpg_ctx *ctx, const int64_t *pk, const double *value, const uint8_t *keep,
+                      int64_t n, int64_t P, const dpg_quantile_params *q, uint64_t *keys,
+                      int64_t *n_keys, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    QtArgs a{};
+    if (const int r = quantile_args(ctx, q, P, &a)) return r;
+    if (n < 0 || !n_keys || (n > 0 && (!pk || !value || !keep || !keys)))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "null argument");
+    if (n >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n must be < 2^31 per device");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int st = DPG_OK;
+    HIP_TRY(hipMemsetAsync(n_keys, 0, 8, s));
+    if (n == 0) return st;
+    ctx->stage_names.clear();
+    ctx->n_events_used = 0;
+    ctx->last_stream = s;
+    WS(raw, uint64_t, "quantile.raw", n);
+    stage(ctx, s, "quantile:keys");
+    const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cu * 16);
+    k_quantile_keys<<<blocks, 256, 0, s>>>(pk, value, keep, (uint32_t)n, (uint64_t)P, a.lo, a.hi, raw,
+                                           reinterpret_cast<unsigned long long *>(n_keys));
+    LAUNCH_CHECK();
+    RsBufs b{raw, nullptr, nullptr, keys, nullptr, nullptr};
+    st = rsort_run(ctx, s, b, (uint32_t)n, n_keys, 0u, 16u + bits_for((uint64_t)P), "quantile:sort");
+    if (st) return st;
+    stage(ctx, s, "quantile:end");
+    return st;
+}
+
+int dpg_quantiles(dpg_ctx *ctx, const uint64_t *keys, const int64_t *n_keys, int64_t P,
+                  const dpg_quantile_params *q, const uint8_t *keep_partition, double *out,
+                  void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    QtArgs a{};
+    if (const int r = quantile_args(ctx, q, P, &a)) return r;
+    if (!n_keys || !out) return fail(ctx, DPG_ERR_INVALID_ARG, "null argument");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // 4 waves per workgroup, one partition per wave at a time
+    const unsigned blocks = (unsigned)std::min<int64_t>((P + 3) / 4, (int64_t)ctx->n_cu * 16);
+    k_quantile_walk<<<blocks, 256, 0, s>>>(keys, reinterpret_cast<const unsigned long long *>(n_keys),
+                                           (uint64_t)P, a, keep_partition, out);
+    LAUNCH_CHECK();
+    return DPG_OK;
 }
 
 }  // extern "C"

@@ -10,7 +10,9 @@ Device pipeline per call (include/dpg.h):
   dpg_bound_aggregate -> [multi-GPU: reduce-scatter of the dense partials,
   or a fixed-block all-to-all of the occupied ones, with every rank's error
   flag: distributed.exchange_partials] -> dpg_select_and_noise ->
-  dpg_compact_kept_async.  The kept count reaches the host when the result's
+  dpg_compact_kept_async.  A plan with percentiles adds dpg_bound_records and
+  dpg_quantile_keys behind the bounding and dpg_quantiles behind the
+  selection, whose columns join the noise kernel's.  The kept count reaches the host when the result's
   ids or values are first read (the one host synchronisation after the
   bounding), so a caller can enqueue the next release first.
 """
@@ -285,6 +287,12 @@ class DeviceAggregation:
                       scale=[0.0] * 4, mid=0.0, mean_const=0, msq_const=0,
                       mean_const_value=0.0, msq_const_value=0.0))
         P = enc.n_partitions
+        percentiles = self.plan is not None and bool(self.plan.percentiles)
+        if percentiles and backend.world_size > 1:
+            # on every rank, before any collective: the kept tree keys would
+            # have to move to their partitions' owners
+            raise NotImplementedError(
+                "percentiles are not built for multi-GPU releases (world_size > 1)")
         if backend.world_size > 1 and not enc.partitions_declared:
             # every rank must use the same dense partition ids and P, or the
             # exchange sums partials of different keys (or hangs)
@@ -327,6 +335,19 @@ class DeviceAggregation:
             ctx.bound_aggregate(_ptr(enc.pid), _ptr(enc.pk),
                                 _ptr(enc.value) if need_values else None,
                                 enc.n, bound, partials, sptr)
+            if percentiles:
+                # the same kept set, record by record, and its sorted tree keys
+                qfields = self.plan.quantile_fields(self.noise_enabled)
+                qp = _native.fill(_native.QuantileParams,
+                                  dict(qfields, pk_offset=0, pk_stride=1, nonce=nonce))
+                rec_keep = torch.empty(max(enc.n, 1), dtype=torch.uint8, device=dev)
+                ctx.bound_records(_ptr(enc.pid), _ptr(enc.pk), enc.n, bound,
+                                  rec_keep.data_ptr(), sptr)
+                qkeys = torch.empty(max(enc.n, 1), dtype=torch.int64, device=dev)
+                n_qkeys = torch.empty(1, dtype=torch.int64, device=dev)
+                ctx.quantile_keys(_ptr(enc.pk), _ptr(enc.value), rec_keep.data_ptr(), enc.n, P,
+                                  qp, qkeys.data_ptr(), n_qkeys.data_ptr(), sptr)
+                self.last_record_keep = rec_keep[:enc.n]
             stage_ms = {}
             tensors = dict(rows=rows, count=count, sum=sum_, nsum=nsum, nsq=nsq)
             self.last_partials = tensors
@@ -361,6 +382,14 @@ class DeviceAggregation:
             keep = torch.empty(local_P, dtype=torch.uint8, device=dev)
             out = torch.empty(max(local_P * n_out, 1), **f64)
             ctx.select_and_noise(lp, sel, nz, keep.data_ptr(), out.data_ptr(), sptr)
+            if percentiles:
+                Q = qfields["n_quantiles"]
+                qout = torch.zeros((local_P, Q), **f64)
+                ctx.quantiles(qkeys.data_ptr(), n_qkeys.data_ptr(), local_P, qp, keep.data_ptr(),
+                              qout.data_ptr(), sptr)
+                out = (torch.cat([out[:local_P * n_out].view(local_P, n_out), qout], dim=1)
+                       .contiguous().view(-1) if n_out else qout.view(-1))
+                n_out += Q
             ids = torch.empty(local_P, dtype=torch.int64, device=dev)
             kept_out = torch.empty(max(local_P * n_out, 1), **f64)
             fields = self.plan.fields if self.plan is not None else ()

@@ -95,6 +95,11 @@ class DPEngine:
             raise NotImplementedError(
                 "custom combiners run arbitrary Python per accumulator and are not "
                 "supported on the MI355X backend (see DESIGN.md)")
+        if (any(m.is_percentile for m in params.metrics or [])
+                and not self._backend.percentiles):
+            raise NotImplementedError(
+                "PERCENTILE metrics are opt-in on the MI355X backend: construct it with "
+                "MI355XBackend(..., percentiles=True) (see DESIGN.md section 11)")
         plan = combiners.CompoundPlan(params, self._budget_accountant)
         public = public_partitions is not None
         if public and not params.public_partitions_already_filtered:

@@ -219,10 +219,16 @@ class MI355XBackend(_HostCollectionOps, PipelineBackend):
         data, no host synchronisation), 'reduce_scatter' (dense) or
         'all_to_all' (fixed blocks of the occupied partitions' rows).
         Partition pk is owned by rank pk mod world_size.
+      percentiles: opt in to Metrics.PERCENTILE.  Off
+        by default, where DPEngine.aggregate raises NotImplementedError for
+        them as before: the route costs about 12 times the tuned bounding,
+        runs on one GPU only, and its parity with PyDP's QuantileTree is
+        pinned to a restatement, not to PyDP.
     """
 
     def __init__(self, device: Optional[int] = None, seed: Optional[int] = None,
-                 process_group=None, exchange: str = "auto"):
+                 process_group=None, exchange: str = "auto", percentiles: bool = False):
+        self.percentiles = bool(percentiles)
         if exchange not in ("auto", "reduce_scatter", "all_to_all"):
             raise ValueError(f"unknown exchange {exchange!r}")
         self.exchange = exchange
