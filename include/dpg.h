@@ -40,6 +40,10 @@
  *        (privacy id, partition) accumulator, merged per partition, then
  *        compute_quantiles) on the records contribution bounding keeps
  *        (contribution_bounders.py:66-105).
+ *   dpg_vector_index / dpg_vector_sums / dpg_vector_clip_noise <-
+ *        VectorSumCombiner (pipeline_dp/combiners.py: the per-partition sum of
+ *        the kept records' vectors) with dp_computations.py _clip_vector and
+ *        add_noise_vector at the release.
  */
 #ifndef DPG_H_
 #define DPG_H_
@@ -105,6 +109,9 @@ extern "C" {
 /* quantile tree: node nu of a partition draws from slot DPG_SLOT_QNODE0 + nu
  * (root = node 0, children of node i = 16 i + 1 .. 16 i + 16) */
 #define DPG_SLOT_QNODE0 16
+/* VECTOR_SUM: coordinate d of a partition draws from slot DPG_SLOT_VEC0 + d
+ * (clear of DPG_SLOT_QNODE0 + node, which stays below 69921) */
+#define DPG_SLOT_VEC0 (1u << 20)
 
 /* value-vector entries an output column can be mapped from */
 #define DPG_V_COUNT 0
@@ -507,9 +514,58 @@ int dpg_quantiles(dpg_ctx *ctx, const uint64_t *keys, const int64_t *n_keys, int
                   const dpg_quantile_params *qparams, const uint8_t *keep_partition, double *out,
                   void *stream);
 
+/* ---- VECTOR_SUM: per-partition vector sums over the kept records ---- */
+#define DPG_NORM_LINF 0
+#define DPG_NORM_L1 1
+#define DPG_NORM_L2 2
+#define DPG_VECTOR_MAX_SIZE 4096
+#define DPG_VSUM_CHUNK 512 /* sorted rows summed by one wave */
+
+/* The inverted index of the kept records: keys[0, *n_keys) (device uint64[n],
+ * device int64) receive pk << 31 | i of every record i with keep[i] != 0 and
+ * pk in [0, P), ascending: the records of a partition are consecutive, in
+ * input order.  n < 2^31 (else DPG_ERR_UNSUPPORTED), P < 2^32 - 1; n == 0
+ * gives *n_keys = 0.  Stream-ordered, no host synchronisation. */
+int dpg_vector_index(dpg_ctx *ctx, const int64_t *pk, const uint8_t *keep, int64_t n,
+                     int64_t n_partitions, uint64_t *keys, int64_t *n_keys, void *stream);
+
+/* out[k][d] (device double[P][D], zero-filled by the call) = the sum of
+ * value[i][d] (device double[n][D], row-major) over the keys of partition k.
+ * No atomics: the order of the additions is a fixed function of the sorted
+ * keys and D (csrc/dpg_vsum.h states it), so two calls agree bit for bit on
+ * any grid.  keys / n_keys as dpg_vector_index wrote them.  1 <= D <=
+ * DPG_VECTOR_MAX_SIZE (larger: DPG_ERR_UNSUPPORTED, as n >= 2^31).
+ * Stream-ordered, no host synchronisation. */
+int dpg_vector_sums(dpg_ctx *ctx, const uint64_t *keys, const int64_t *n_keys, const double *value,
+                    int64_t n, int32_t size, int64_t n_partitions, double *out, void *stream);
+
+typedef struct dpg_vector_params {
+    int32_t size;       /* D = vector_size                                   */
+    int32_t norm_kind;  /* DPG_NORM_*                                        */
+    double max_norm;    /* vector_max_norm                                   */
+    int32_t noise_kind; /* DPG_NOISE_*                                       */
+    int32_t reserved;
+    double scale;       /* b or sigma of every coordinate                    */
+    int64_t pk_offset;  /* global pk of local partition i is                 */
+    int64_t pk_stride;  /*   pk_offset + i * pk_stride; <= 0 means 1         */
+    uint64_t nonce;     /* per-release nonce (see dpg_bound_params)          */
+} dpg_vector_params;
+
+/* out[k][d] = add_noise(kind, clip(sums[k])[d], scale, stream seed,
+ * pk_offset + k * pk_stride, DPG_SLOT_VEC0 + d) for the rows (device
+ * double[P][D]) with keep_partition[k] != 0 (device uint8[P], or NULL: all);
+ * the other rows of out are left untouched.  clip: DPG_NORM_LINF clamps
+ * every coordinate to [-max_norm, max_norm]; DPG_NORM_L1 / L2 scale the row
+ * by min(1, max_norm / norm), 1 for a zero row.  out may be sums.
+ * Stream-ordered, no host synchronisation. */
+int dpg_vector_clip_noise(dpg_ctx *ctx, const double *sums, int64_t n_partitions,
+                          const dpg_vector_params *vparams, const uint8_t *keep_partition,
+                          double *out, void *stream);
+
 /* Timing/profiling aid: per-stage device time (ms) of the last
  * dpg_bound_aggregate / dpg_preaggregate / dpg_dataset_histograms /
- * dpg_bound_records / dpg_quantile_keys call,
+ * dpg_bound_records / dpg_quantile_keys / dpg_vector_index / dpg_vector_sums
+ * call ("vector:keys", "vector:sort:...", "vector:sum", "vector:merge"),
  * measured with HIP events on its stream (waits for the last event).
  * names (comma separated, <= names_len bytes): e.g. "begin",
  * "partition1:hist", "partition1:scatter", "partition2:hist",

@@ -23,7 +23,8 @@ EXPORTED = ("dpg_ctx_create", "dpg_ctx_destroy", "dpg_last_error", "dpg_set_seed
             "dpg_comm_unique_id", "dpg_ctx_create_comm", "dpg_reduce_scatter_partials",
             "dpg_pack_partials", "dpg_unpack_partials", "dpg_export_error",
             "dpg_import_error", "dpg_shard_records", "dpg_check_shard",
-            "dpg_sort_pairs_u64", "dpg_bound_records", "dpg_quantile_keys", "dpg_quantiles")
+            "dpg_sort_pairs_u64", "dpg_bound_records", "dpg_quantile_keys", "dpg_quantiles",
+            "dpg_vector_index", "dpg_vector_sums", "dpg_vector_clip_noise")
 
 COMM_ID_BYTES = 128  # DPG_COMM_ID_BYTES
 
@@ -32,6 +33,11 @@ SHARD_TILE = 2048  # DPG_SHARD_TILE (csrc/dpg_shard.h): records per workgroup of
 
 SLOT_QNODE0 = 16  # DPG_SLOT_QNODE0: noise slot of quantile-tree node 0
 QUANTILE_MAX = 16  # quantiles per dpg_quantiles call
+
+SLOT_VEC0 = 1 << 20  # DPG_SLOT_VEC0: noise slot of vector coordinate 0
+VECTOR_MAX_SIZE = 4096  # DPG_VECTOR_MAX_SIZE
+VSUM_CHUNK = 512  # DPG_VSUM_CHUNK: sorted rows summed by one wave
+NORM_LINF, NORM_L1, NORM_L2 = 0, 1, 2  # DPG_NORM_*
 
 HIST_INT_BINS = 16300  # DPG_HIST_INT_BINS
 HIST_SUM_BINS = 10000  # DPG_HIST_SUM_BINS
@@ -80,6 +86,16 @@ class QuantileParams(ctypes.Structure):
     _fields_ = [("lo", ctypes.c_double), ("hi", ctypes.c_double),
                 ("noise_kind", ctypes.c_int32), ("n_quantiles", ctypes.c_int32),
                 ("scale", ctypes.c_double), ("quantiles", ctypes.c_double * 16),
+                ("pk_offset", ctypes.c_int64), ("pk_stride", ctypes.c_int64),
+                ("nonce", ctypes.c_uint64)]
+
+
+class VectorParams(ctypes.Structure):
+    """dpg_vector_params: the clip and the per-coordinate noise of VECTOR_SUM."""
+    _fields_ = [("size", ctypes.c_int32), ("norm_kind", ctypes.c_int32),
+                ("max_norm", ctypes.c_double),
+                ("noise_kind", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("scale", ctypes.c_double),
                 ("pk_offset", ctypes.c_int64), ("pk_stride", ctypes.c_int64),
                 ("nonce", ctypes.c_uint64)]
 
@@ -228,6 +244,13 @@ def load():
         lib.dpg_quantile_keys.restype = ctypes.c_int
         lib.dpg_quantiles.argtypes = [vp, vp, vp, i64, ctypes.POINTER(QuantileParams), vp, vp, vp]
         lib.dpg_quantiles.restype = ctypes.c_int
+        lib.dpg_vector_index.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp]
+        lib.dpg_vector_index.restype = ctypes.c_int
+        lib.dpg_vector_sums.argtypes = [vp, vp, vp, vp, i64, i32, i64, vp, vp]
+        lib.dpg_vector_sums.restype = ctypes.c_int
+        lib.dpg_vector_clip_noise.argtypes = [vp, vp, i64, ctypes.POINTER(VectorParams), vp, vp,
+                                              vp]
+        lib.dpg_vector_clip_noise.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -366,6 +389,26 @@ class Context:
         st = self.lib.dpg_quantiles(self.handle, keys_ptr, n_keys_ptr, n_partitions,
                                     ctypes.byref(q), keep_partition_ptr, out_ptr, stream)
         self.check(st, "dpg_quantiles")
+
+    def vector_index(self, pk_ptr, keep_ptr, n, n_partitions, keys_ptr, n_keys_ptr, stream):
+        """Sorted keys (pk << 31 | record index) of the kept records."""
+        st = self.lib.dpg_vector_index(self.handle, pk_ptr, keep_ptr, n, n_partitions, keys_ptr,
+                                       n_keys_ptr, stream)
+        self.check(st, "dpg_vector_index")
+
+    def vector_sums(self, keys_ptr, n_keys_ptr, value_ptr, n, size, n_partitions, out_ptr, stream):
+        """Device double[P][size] at out_ptr: the per-partition sums of the
+        indexed rows of value (double[n][size]), in a fixed order."""
+        st = self.lib.dpg_vector_sums(self.handle, keys_ptr, n_keys_ptr, value_ptr, n, size,
+                                      n_partitions, out_ptr, stream)
+        self.check(st, "dpg_vector_sums")
+
+    def vector_clip_noise(self, sums_ptr, n_partitions, v: VectorParams, keep_partition_ptr,
+                          out_ptr, stream):
+        """Clips every kept partition's summed vector and noises its coordinates."""
+        st = self.lib.dpg_vector_clip_noise(self.handle, sums_ptr, n_partitions, ctypes.byref(v),
+                                            keep_partition_ptr, out_ptr, stream)
+        self.check(st, "dpg_vector_clip_noise")
 
     def select_and_noise(self, partials: Partials, sel: SelectParams, noise: NoiseParams,
                          keep_ptr, out_ptr, stream):

@@ -32,6 +32,8 @@ _FIELD_SOURCE = {"count": V_COUNT, "sum": V_SUM, "mean": V_MEAN,
 
 QUANTILE_TREE_HEIGHT = 4  # csrc/dpg_quantile.h: 16-ary, 65536 leaves
 QUANTILE_MAX = 16         # dpg_quantile_params.quantiles
+VECTOR_MAX_SIZE = 4096    # DPG_VECTOR_MAX_SIZE
+NORM_LINF, NORM_L1, NORM_L2 = 0, 1, 2
 
 
 def percentile_field(p) -> str:
@@ -40,6 +42,8 @@ def percentile_field(p) -> str:
         return f"percentile_{int(p)}"
     return "percentile_" + str(p).replace(".", "_")
 
+
+_NORM_KINDS = {agg.NormKind.Linf: NORM_LINF, agg.NormKind.L1: NORM_L1, agg.NormKind.L2: NORM_L2}
 
 _named_tuples: Dict[Tuple[str, ...], type] = {}
 
@@ -57,14 +61,31 @@ class CompoundPlan:
     """What one DPEngine.aggregate call computes on the device."""
 
     def __init__(self, params: agg.AggregateParams,
-                 accountant: budget_accounting.BudgetAccountant):
+                 accountant: budget_accounting.BudgetAccountant, vector_sums: bool = False):
         self.params = params
         metrics = set(params.metrics or [])
         unsupported = [m for m in metrics if m == agg.Metrics.VECTOR_SUM]
-        if unsupported:
+        if unsupported and not vector_sums:
             raise NotImplementedError(
-                f"{unsupported} are not supported by the MI355X backend "
-                f"(see DESIGN.md, out of scope)")
+                f"{unsupported} are not supported by the MI355X backend unless it is built "
+                f"with vector_sums=True (see DESIGN.md section 12)")
+        self.vector_size: Optional[int] = None
+        if unsupported:
+            if any(m.is_percentile for m in metrics):
+                raise NotImplementedError(
+                    "VECTOR_SUM and PERCENTILE metrics cannot share one aggregation: the value "
+                    "column is either a vector or a scalar")
+            missing = [n for n in ("vector_size", "vector_max_norm", "vector_norm_kind")
+                       if getattr(params, n) is None]
+            if missing:
+                raise ValueError(f"VECTOR_SUM needs {', '.join(missing)}")
+            if params.vector_norm_kind not in _NORM_KINDS:
+                raise NotImplementedError(
+                    f"vector_norm_kind {params.vector_norm_kind} is not supported")
+            if not 1 <= int(params.vector_size) <= VECTOR_MAX_SIZE:
+                raise NotImplementedError(
+                    f"vector_size must be in [1, {VECTOR_MAX_SIZE}], got {params.vector_size}")
+            self.vector_size = int(params.vector_size)
         mech = params.noise_kind.convert_to_mechanism_type()
         w = params.budget_weight
         self.noise_kind = params.noise_kind
@@ -107,6 +128,10 @@ class CompoundPlan:
             fields.append("privacy_id_count")
             self.mask |= M_PID
             self._pid_sens = dpc.sensitivities_for_privacy_id_count(params)
+        # combiners.py: the VectorSumCombiner follows the privacy-id count
+        if self.vector_size is not None:
+            self.specs["vector_sum"] = accountant.request_budget(mech, weight=w)
+            fields.append("vector_sum")
         # combiners.py:839-856: one QuantileCombiner for every percentile, one
         # budget request, fields in the order of params.metrics
         self.percentiles: List[float] = [m.parameter for m in (params.metrics or [])
@@ -119,7 +144,9 @@ class CompoundPlan:
                 raise ValueError("percentiles need min_value and max_value")
             self.specs["percentile"] = accountant.request_budget(mech, weight=w)
             fields += [percentile_field(p) for p in self.percentiles]
-        self.n_noise_outputs = len(fields) - len(self.percentiles)
+        # the columns of the selection / noise kernel: not the percentiles', not the vector's
+        self.n_noise_outputs = (len(fields) - len(self.percentiles)
+                                - (1 if self.vector_size is not None else 0))
         self.fields = tuple(fields)
         self.MetricsTuple = metrics_tuple_type(self.fields)
         self._mechanisms = None
@@ -127,7 +154,7 @@ class CompoundPlan:
     # ------------------------------------------------------------ bounding
     def expects_per_partition_sampling(self) -> bool:
         """combiners.py:76-85, 323-324, 364-365, 738-739."""
-        if self.percentiles:
+        if self.percentiles or self.vector_size is not None:
             return True
         if self.family != FAMILY_SCALAR or "count" in self.specs:
             return True
@@ -151,7 +178,8 @@ class CompoundPlan:
         return SUM_CLIP_VALUE
 
     def needs_values(self) -> bool:
-        return bool(self.mask & (M_SUM | M_MEAN | M_VARIANCE)) or bool(self.percentiles)
+        return (bool(self.mask & (M_SUM | M_MEAN | M_VARIANCE)) or bool(self.percentiles)
+                or self.vector_size is not None)
 
     def bound_fields(self, n_partitions: int) -> dict:
         """Field values of dpg_bound_params."""
@@ -273,6 +301,24 @@ class CompoundPlan:
                     n_quantiles=len(self.percentiles),
                     scale=float(self.quantile_mechanism().scale),
                     quantiles=[p / 100.0 for p in self.percentiles])
+
+    def vector_fields(self, with_noise: bool = True) -> dict:
+        """Field values of dpg_vector_params but the partition offset, stride
+        and nonce (after compute_budgets()).  The scale is the reference's
+        (CombinerParams.additive_vector_noise_params, add_noise_vector):
+        every coordinate gets eps / D and delta / D with l0 =
+        max_partitions_contributed and linf = max_contributions_per_partition;
+        vector_max_norm does not enter it."""
+        p = self.params
+        kind = {agg.NoiseKind.LAPLACE: NOISE_LAPLACE,
+                agg.NoiseKind.GAUSSIAN: NOISE_GAUSSIAN}[self.noise_kind]
+        spec = self.specs["vector_sum"]
+        D = self.vector_size
+        scale = dpc.noise_scale(self.noise_kind, spec.eps / D, spec.delta / D,
+                                p.max_partitions_contributed, p.max_contributions_per_partition)
+        return dict(size=D, norm_kind=_NORM_KINDS[p.vector_norm_kind],
+                    max_norm=float(p.vector_max_norm),
+                    noise_kind=kind if with_noise else NOISE_NONE, scale=float(scale))
 
     # ------------------------------------------------------------ report
     def explain_computation(self) -> List:

@@ -77,6 +77,7 @@ static hipError_t set_func_attr(const void *kern, hipFuncAttribute attr, int val
 #include "dpg_sortmw.h"
 #include "dpg_team.h"
 #include "dpg_utility.h"
+#include "dpg_vsum.h"
 #include "dpg_wave.h"
 
 using namespace dpg;
@@ -3042,6 +3043,115 @@ int dpg_quantiles(dpg_ctx *ctx, const uint64_t *keys, const int64_t *n_keys, int
     const unsigned blocks = (unsigned)std::min<int64_t>((P + 3) / 4, (int64_t)ctx->n_cu * 16);
     k_quantile_walk<<<blocks, 256, 0, s>>>(keys, reinterpret_cast<const unsigned long long *>(n_keys),
                                            (uint64_t)P, a, keep_partition, out);
+    LAUNCH_CHECK();
+    return DPG_OK;
+}
+
+// ---- VECTOR_SUM: inverted index, per-partition vector sums, clip and noise
+
+int dpg_vector_index(dpg_ctx *ctx, const int64_t *pk, const uint8_t *keep, int64_t n, int64_t P,
+                     uint64_t *keys, int64_t *n_keys, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (P <= 0 || P >= 0xFFFFFFFFll)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "n_partitions must be in [1, 2^32-1)");
+    if (n < 0 || !n_keys || (n > 0 && (!pk || !keep || !keys)))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "null argument");
+    if (n >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n must be < 2^31 per device");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int st = DPG_OK;
+    HIP_TRY(hipMemsetAsync(n_keys, 0, 8, s));
+    if (n == 0) return st;
+    ctx->stage_names.clear();
+    ctx->n_events_used = 0;
+    ctx->last_stream = s;
+    WS(raw, uint64_t, "vector.raw", n);
+    stage(ctx, s, "vector:keys");
+    const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cu * 16);
+    k_vector_keys<<<blocks, 256, 0, s>>>(pk, keep, (uint32_t)n, (uint64_t)P, raw,
+                                         reinterpret_cast<unsigned long long *>(n_keys));
+    LAUNCH_CHECK();
+    RsBufs b{raw, nullptr, nullptr, keys, nullptr, nullptr};
+    st = rsort_run(ctx, s, b, (uint32_t)n, n_keys, 0u, 31u + bits_for((uint64_t)P), "vector:sort");
+    if (st) return st;
+    stage(ctx, s, "vector:end");
+    return st;
+}
+
+int dpg_vector_sums(dpg_ctx *ctx, const uint64_t *keys, const int64_t *n_keys, const double *value,
+                    int64_t n, int32_t D, int64_t P, double *out, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (P <= 0 || P >= 0xFFFFFFFFll)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "n_partitions must be in [1, 2^32-1)");
+    if (D < 1) return fail(ctx, DPG_ERR_INVALID_ARG, "the vector size must be positive");
+    if (n < 0 || !n_keys || !out || (n > 0 && (!keys || !value)))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "null argument");
+    if (D > DPG_VECTOR_MAX_SIZE)
+        return fail(ctx, DPG_ERR_UNSUPPORTED, "the vector size must be <= DPG_VECTOR_MAX_SIZE");
+    if (n >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n must be < 2^31 per device");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int st = DPG_OK;
+    HIP_TRY(hipMemsetAsync(out, 0, sizeof(double) * (size_t)P * (size_t)D, s));
+    if (n == 0) return st;
+    ctx->stage_names.clear();
+    ctx->n_events_used = 0;
+    ctx->last_stream = s;
+    // the launches are sized by n; chunks past the device's n_keys do nothing
+    const int64_t nchunks = (n + DPG_VSUM_CHUNK - 1) / DPG_VSUM_CHUNK;
+    WS(part, double, "vector.part", (size_t)nchunks * 2 * (size_t)D);
+    WS(hpk, uint32_t, "vector.hpk", nchunks);
+    WS(tpk, uint32_t, "vector.tpk", nchunks);
+    stage(ctx, s, "vector:sum");
+    {  // 4 waves per workgroup, one chunk per wave at a time, 16 waves per CU
+        const unsigned blocks = (unsigned)std::min<int64_t>((nchunks + 3) / 4, (int64_t)ctx->n_cu * 4);
+        k_vsum_chunks<<<blocks, 256, 0, s>>>(keys, n_keys, value, (uint32_t)n, (uint32_t)D,
+                                             (uint64_t)P, out, part, hpk, tpk);
+        LAUNCH_CHECK();
+    }
+    stage(ctx, s, "vector:merge");
+    {
+        int64_t group = 1;  // lanes per chunk: D rounded up to a power of two, at most a wave
+        while (group < D && group < 64) group <<= 1;
+        const int64_t per_block = 256 / group;
+        const unsigned blocks = (unsigned)std::min<int64_t>((nchunks + per_block - 1) / per_block,
+                                                            (int64_t)ctx->n_cu * 16);
+        k_vsum_merge<<<blocks, 256, 0, s>>>(n_keys, (uint32_t)n, (uint32_t)D, (uint64_t)P, part, hpk,
+                                            tpk, out);
+        LAUNCH_CHECK();
+    }
+    stage(ctx, s, "vector:end");
+    return st;
+}
+
+int dpg_vector_clip_noise(dpg_ctx *ctx, const double *sums, int64_t P, const dpg_vector_params *v,
+                          const uint8_t *keep_partition, double *out, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (!v || !sums || !out) return fail(ctx, DPG_ERR_INVALID_ARG, "null argument");
+    if (P <= 0 || P >= 0xFFFFFFFFll)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "n_partitions must be in [1, 2^32-1)");
+    if (v->size < 1) return fail(ctx, DPG_ERR_INVALID_ARG, "the vector size must be positive");
+    if (v->norm_kind < DPG_NORM_LINF || v->norm_kind > DPG_NORM_L2)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "bad norm_kind");
+    if (v->noise_kind < DPG_NOISE_NONE || v->noise_kind > DPG_NOISE_GAUSSIAN)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "bad noise_kind");
+    if (!(v->max_norm >= 0.0)) return fail(ctx, DPG_ERR_INVALID_ARG, "max_norm must be >= 0");
+    if (v->size > DPG_VECTOR_MAX_SIZE)
+        return fail(ctx, DPG_ERR_UNSUPPORTED, "the vector size must be <= DPG_VECTOR_MAX_SIZE");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    VcArgs a{};
+    a.D = (uint32_t)v->size;
+    a.norm_kind = v->norm_kind;
+    a.noise_kind = v->noise_kind;
+    a.max_norm = v->max_norm;
+    a.scale = v->scale;
+    a.pk_offset = v->pk_offset;
+    a.pk_stride = v->pk_stride > 0 ? v->pk_stride : 1;
+    a.seed = stream_seed(ctx->seed, v->nonce);
+    // 4 waves per workgroup, one partition per wave at a time
+    const unsigned blocks = (unsigned)std::min<int64_t>((P + 3) / 4, (int64_t)ctx->n_cu * 16);
+    k_vector_clip_noise<<<blocks, 256, 0, s>>>(sums, (uint64_t)P, a, keep_partition, out);
     LAUNCH_CHECK();
     return DPG_OK;
 }

@@ -12,7 +12,10 @@ Device pipeline per call (include/dpg.h):
   flag: distributed.exchange_partials] -> dpg_select_and_noise ->
   dpg_compact_kept_async.  A plan with percentiles adds dpg_bound_records and
   dpg_quantile_keys behind the bounding and dpg_quantiles behind the
-  selection, whose columns join the noise kernel's.  The kept count reaches the host when the result's
+  selection, whose columns join the noise kernel's.  A plan with VECTOR_SUM
+  adds dpg_bound_records, dpg_vector_index and dpg_vector_sums behind the
+  bounding and dpg_vector_clip_noise behind the selection; its D columns come
+  last.  The kept count reaches the host when the result's
   ids or values are first read (the one host synchronisation after the
   bounding), so a caller can enqueue the next release first.
 """
@@ -64,8 +67,9 @@ def check_dropped(block: bool = False) -> None:
 
 class DeviceResult:
     """Materialised result: kept partition ids (int64 [K], global dense ids)
-    and their metric columns (float64 [K, len(fields)]), on the device.
-    `keys()` maps ids back to the user's partition keys.
+    and their metric columns (float64 [K, len(fields)]), on the device; with
+    VECTOR_SUM the last field `vector_sum` takes the last vector_size columns
+    ([K, n_scalar + D]).  `keys()` maps ids back to the user's partition keys.
 
     Built from the compaction's full-size outputs and its device info word
     (kept count, bounding error bits): the count is read -- and an internal
@@ -172,7 +176,13 @@ class DeviceAggregation:
             return iter(keys)
         vals = res.values.cpu().numpy()
         T = self.plan.MetricsTuple
-        return iter([(k, T(*map(float, row))) for k, row in zip(keys, vals)])
+        D = self.plan.vector_size
+        if D is None:
+            return iter([(k, T(*map(float, row))) for k, row in zip(keys, vals)])
+        # the vector's D columns are the last ones; its field is the last one
+        ns = vals.shape[1] - D
+        return iter([(k, T(*map(float, row[:ns]), row[ns:].copy()))
+                     for k, row in zip(keys, vals)])
 
     def materialize(self, gather: bool = True) -> DeviceResult:
         if self._result is None:
@@ -299,6 +309,19 @@ class DeviceAggregation:
             raise ValueError(
                 "multi-GPU aggregation needs globally dense integer partition ids: "
                 "pass ColumnarData(..., n_partitions=P) with pk in [0, P) on every rank")
+        vector = self.plan.vector_size if self.plan is not None else None
+        if vector is not None and backend.world_size > 1:
+            # on every rank, before any collective: the kept rows would have
+            # to move to their partitions' owners
+            raise NotImplementedError(
+                "VECTOR_SUM is not built for multi-GPU releases (world_size > 1)")
+        if vector is not None:
+            # the reference's error class for a vector of another size
+            if enc.value.dim() != 2 or tuple(enc.value.shape) != (enc.n, vector):
+                raise TypeError(
+                    f"Shape mismatch: the value column has shape {tuple(enc.value.shape)}, "
+                    f"VECTOR_SUM with vector_size={vector} needs ({enc.n}, {vector})")
+            enc.value = enc.value.to(torch.float64).contiguous()
         self._place_records(enc)
         bfields = self._bound_fields(P)
         l0 = (bfields["max_contributions"] if bfields["mode"] == combiners.MODE_PER_PID
@@ -332,9 +355,27 @@ class DeviceAggregation:
                                         sum_.data_ptr() if sum_ is not None else None,
                                         nsum.data_ptr() if nsum is not None else None,
                                         nsq.data_ptr() if nsq is not None else None)
+            # a vector column is [n, D]: the bounding has no value lanes then
+            # (VECTOR_SUM excludes SUM / MEAN / VARIANCE) and must not see it
             ctx.bound_aggregate(_ptr(enc.pid), _ptr(enc.pk),
-                                _ptr(enc.value) if need_values else None,
+                                _ptr(enc.value) if need_values and vector is None else None,
                                 enc.n, bound, partials, sptr)
+            if vector is not None:
+                # the same kept set, record by record, indexed by partition,
+                # and the unclipped sums of its rows
+                vfields = self.plan.vector_fields(self.noise_enabled)
+                rec_keep = torch.empty(max(enc.n, 1), dtype=torch.uint8, device=dev)
+                ctx.bound_records(_ptr(enc.pid), _ptr(enc.pk), enc.n, bound,
+                                  rec_keep.data_ptr(), sptr)
+                vkeys = torch.empty(max(enc.n, 1), dtype=torch.int64, device=dev)
+                n_vkeys = torch.empty(1, dtype=torch.int64, device=dev)
+                ctx.vector_index(_ptr(enc.pk), rec_keep.data_ptr(), enc.n, P,
+                                 vkeys.data_ptr(), n_vkeys.data_ptr(), sptr)
+                vsums = torch.empty((P, vector), **f64)
+                ctx.vector_sums(vkeys.data_ptr(), n_vkeys.data_ptr(), _ptr(enc.value), enc.n,
+                                vector, P, vsums.data_ptr(), sptr)
+                self.last_record_keep = rec_keep[:enc.n]
+                self.last_vector_sums = vsums
             if percentiles:
                 # the same kept set, record by record, and its sorted tree keys
                 qfields = self.plan.quantile_fields(self.noise_enabled)
@@ -390,6 +431,16 @@ class DeviceAggregation:
                 out = (torch.cat([out[:local_P * n_out].view(local_P, n_out), qout], dim=1)
                        .contiguous().view(-1) if n_out else qout.view(-1))
                 n_out += Q
+            if vector is not None:
+                vp = _native.fill(_native.VectorParams,
+                                  dict(vfields, pk_offset=pk_offset, pk_stride=pk_stride,
+                                       nonce=nonce))
+                vout = torch.zeros((local_P, vector), **f64)
+                ctx.vector_clip_noise(vsums.data_ptr(), local_P, vp, keep.data_ptr(),
+                                      vout.data_ptr(), sptr)
+                out = (torch.cat([out[:local_P * n_out].view(local_P, n_out), vout], dim=1)
+                       .contiguous().view(-1) if n_out else vout.view(-1))
+                n_out += vector
             ids = torch.empty(local_P, dtype=torch.int64, device=dev)
             kept_out = torch.empty(max(local_P * n_out, 1), **f64)
             fields = self.plan.fields if self.plan is not None else ()

@@ -100,7 +100,12 @@ class DPEngine:
             raise NotImplementedError(
                 "PERCENTILE metrics are opt-in on the MI355X backend: construct it with "
                 "MI355XBackend(..., percentiles=True) (see DESIGN.md section 11)")
-        plan = combiners.CompoundPlan(params, self._budget_accountant)
+        vector = agg.Metrics.VECTOR_SUM in (params.metrics or [])
+        if vector and not self._backend.vector_sums:
+            raise NotImplementedError(
+                "the VECTOR_SUM metric is opt-in on the MI355X backend: construct it with "
+                "MI355XBackend(..., vector_sums=True) (see DESIGN.md section 12)")
+        plan = combiners.CompoundPlan(params, self._budget_accountant, vector_sums=vector)
         public = public_partitions is not None
         if public and not params.public_partitions_already_filtered:
             self._add_report_stage(

@@ -224,11 +224,18 @@ class MI355XBackend(_HostCollectionOps, PipelineBackend):
         them as before: the route costs about 12 times the tuned bounding,
         runs on one GPU only, and its parity with PyDP's QuantileTree is
         pinned to a restatement, not to PyDP.
+      vector_sums: opt in to Metrics.VECTOR_SUM.  Off
+        by default, where DPEngine.aggregate raises NotImplementedError for it
+        as before: the route sorts the kept records once more, runs on one
+        GPU only, and its noise scale is the reference's calibration
+        (eps / D per coordinate, vector_max_norm not in it), reproduced.
     """
 
     def __init__(self, device: Optional[int] = None, seed: Optional[int] = None,
-                 process_group=None, exchange: str = "auto", percentiles: bool = False):
+                 process_group=None, exchange: str = "auto", percentiles: bool = False,
+                 vector_sums: bool = False):
         self.percentiles = bool(percentiles)
+        self.vector_sums = bool(vector_sums)
         if exchange not in ("auto", "reduce_scatter", "all_to_all"):
             raise ValueError(f"unknown exchange {exchange!r}")
         self.exchange = exchange
