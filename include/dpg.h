@@ -452,6 +452,33 @@ int dpg_shard_records(dpg_ctx *ctx, const int64_t *pid, const int64_t *pk, const
 int dpg_check_shard(dpg_ctx *ctx, const int64_t *pid, int64_t n, int nranks, int rank,
                     int64_t *n_bad, void *stream);
 
+/* ---- multi-GPU: partition-keyed items to the rank that owns their partition ----
+ * A release with percentiles or VECTOR_SUM sends its kept tree keys, or the
+ * occupied partitions of its per-rank vector sums, to the partitions' owners
+ * (pk mod nranks, distributed.owner_of) between the bounding and the
+ * selection (distributed.exchange_owner_keys; csrc/dpg_owner.h).
+ *
+ * Stable split of keys[0, *n_keys) (device uint64[n_max]; *n_keys is a device int64,
+ * *n_keys <= n_max < 2^31) by the owner of their partition.
+ *   pk    = key >> low_bits           (pk < 2^32 - 1, 0 <= low_bits <= 32)
+ *   owner = pk % nranks               (1 <= nranks <= DPG_SHARD_MAX_RANKS)
+ * out_keys (device uint64[n_max]) is destination-major, in input order within
+ * a destination: the keys of destination d occupy [sum(counts[0..d)), +counts[d]).
+ * Each key is rewritten for its owner as
+ *   (pk / nranks) << low_bits | (key & (2^low_bits - 1)).
+ * out_src (device uint32[n_max], may be NULL) is the input position of every
+ * output entry. counts is a device int64[nranks].
+ * Entries past *n_keys are neither read nor written. *n_keys == 0 gives
+ * all-zero counts (n_max == 0 too: the key pointers may then be NULL).
+ * nranks or low_bits out of range, n_max < 0 or a NULL n_keys / counts:
+ * DPG_ERR_INVALID_ARG; n_max >= 2^31: DPG_ERR_UNSUPPORTED; both before any
+ * device work.
+ * Stream-ordered, no host synchronisation. */
+int dpg_owner_split_keys(dpg_ctx *ctx, const uint64_t *keys, const int64_t *n_keys,
+                         int64_t n_max, int32_t low_bits, int nranks,
+                         uint64_t *out_keys, uint32_t *out_src, int64_t *counts,
+                         void *stream);
+
 /* ---- percentiles: kept records, quantile tree (combiners.py:532-611) ----
  * Stable LSD radix sort of n (key, payload) pairs by the key bits
  * [begin_bit, end_bit) (0 <= begin_bit <= end_bit <= 64), 8 bits per pass;
@@ -565,7 +592,8 @@ int dpg_vector_clip_noise(dpg_ctx *ctx, const double *sums, int64_t n_partitions
 /* Timing/profiling aid: per-stage device time (ms) of the last
  * dpg_bound_aggregate / dpg_preaggregate / dpg_dataset_histograms /
  * dpg_bound_records / dpg_quantile_keys / dpg_vector_index / dpg_vector_sums
- * call ("vector:keys", "vector:sort:...", "vector:sum", "vector:merge"),
+ * / dpg_owner_split_keys call ("vector:keys", "vector:sort:...", "vector:sum",
+ * "vector:merge"; "owner:count", "owner:scan", "owner:scatter"),
  * measured with HIP events on its stream (waits for the last event).
  * names (comma separated, <= names_len bytes): e.g. "begin",
  * "partition1:hist", "partition1:scatter", "partition2:hist",

@@ -23,7 +23,7 @@ EXPORTED = ("dpg_ctx_create", "dpg_ctx_destroy", "dpg_last_error", "dpg_set_seed
             "dpg_comm_unique_id", "dpg_ctx_create_comm", "dpg_reduce_scatter_partials",
             "dpg_pack_partials", "dpg_unpack_partials", "dpg_export_error",
             "dpg_import_error", "dpg_shard_records", "dpg_check_shard",
-            "dpg_sort_pairs_u64", "dpg_bound_records", "dpg_quantile_keys", "dpg_quantiles",
+            "dpg_owner_split_keys", "dpg_sort_pairs_u64", "dpg_bound_records", "dpg_quantile_keys", "dpg_quantiles",
             "dpg_vector_index", "dpg_vector_sums", "dpg_vector_clip_noise")
 
 COMM_ID_BYTES = 128  # DPG_COMM_ID_BYTES
@@ -235,6 +235,8 @@ def load():
         lib.dpg_shard_records.restype = ctypes.c_int
         lib.dpg_check_shard.argtypes = [vp, vp, i64, ctypes.c_int, ctypes.c_int, vp, vp]
         lib.dpg_check_shard.restype = ctypes.c_int
+        lib.dpg_owner_split_keys.argtypes = [vp, vp, vp, i64, i32, ctypes.c_int, vp, vp, vp, vp]
+        lib.dpg_owner_split_keys.restype = ctypes.c_int
         lib.dpg_sort_pairs_u64.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
         lib.dpg_sort_pairs_u64.restype = ctypes.c_int
         lib.dpg_bound_records.argtypes = [vp, vp, vp, i64, ctypes.POINTER(BoundParams), vp, vp]
@@ -360,6 +362,16 @@ class Context:
         """Device int64 at n_bad_ptr = records whose owner is not `rank`."""
         st = self.lib.dpg_check_shard(self.handle, pid_ptr, n, nranks, rank, n_bad_ptr, stream)
         self.check(st, "dpg_check_shard")
+
+    def owner_split_keys(self, keys_ptr, n_keys_ptr, n_max, low_bits, nranks, out_keys_ptr,
+                         out_src_ptr, counts_ptr, stream):
+        """Stable split of the first *n_keys_ptr (device int64) keys by the
+        owner (key >> low_bits) % nranks into out_keys, destination-major and
+        re-based to the owner's local partition ids; out_src (or None): the
+        input positions; counts (device int64[nranks])."""
+        st = self.lib.dpg_owner_split_keys(self.handle, keys_ptr, n_keys_ptr, n_max, low_bits,
+                                           nranks, out_keys_ptr, out_src_ptr, counts_ptr, stream)
+        self.check(st, "dpg_owner_split_keys")
 
     def sort_pairs_u64(self, keys_in_ptr, vals_in_ptr, n, begin_bit, end_bit, keys_out_ptr,
                        vals_out_ptr, stream):

@@ -67,6 +67,7 @@ static hipError_t set_func_attr(const void *kern, hipFuncAttribute attr, int val
 #include "dpg_chunk.h"
 #include "dpg_common.h"
 #include "dpg_hist.h"
+#include "dpg_owner.h"
 #include "dpg_partition.h"
 #include "dpg_quantile.h"
 #include "dpg_records.h"
@@ -2792,6 +2793,62 @@ int dpg_check_shard(dpg_ctx *ctx, const int64_t *pid, int64_t n, int nranks, int
                                                     reinterpret_cast<unsigned long long *>(n_bad));
         LAUNCH_CHECK();
     }
+    return st;
+}
+
+int dpg_owner_split_keys(dpg_ctx *ctx, const uint64_t *keys, const int64_t *n_keys, int64_t n_max,
+                         int32_t low_bits, int nranks, uint64_t *out_keys, uint32_t *out_src,
+                         int64_t *counts, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (nranks < 1 || nranks > DPG_SHARD_MAX_RANKS)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "nranks must be in [1, DPG_SHARD_MAX_RANKS]");
+    if (low_bits < 0 || low_bits > 32)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "low_bits must be in [0, 32]");
+    if (n_max < 0 || !n_keys || !counts)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "n_max < 0, or n_keys or counts is NULL");
+    if (n_max >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n_max must be < 2^31 per device");
+    // n_max == 0 reads and writes no key: the key pointers may be anything
+    if (n_max > 0 && (!keys || !out_keys))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "keys and out_keys must be given");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int st = DPG_OK;
+    if (n_max == 0) {
+        HIP_TRY(hipMemsetAsync(counts, 0, (size_t)nranks * 8, s));
+        return st;
+    }
+    ctx->stage_names.clear();
+    ctx->n_events_used = 0;
+    ctx->last_stream = s;
+    const uint32_t R = (uint32_t)nranks, N = (uint32_t)n_max, lb = (uint32_t)low_bits;
+    uint32_t bits = 0;
+    while ((1u << bits) < R) ++bits;
+    const uint32_t ntiles = (N + DPG_SHARD_TILE - 1) / DPG_SHARD_TILE;
+    const uint32_t M = R * ntiles;  // <= 64 * 2^20
+    const uint32_t nchunks = (M + kScanChunk - 1) / kScanChunk;
+    WS(tiles, uint32_t, "owner.tiles", M);
+    WS(sums, uint32_t, "owner.sums", nchunks);
+    stage(ctx, s, "owner:count");
+    k_owner_count<<<ntiles, kShThreads, 0, s>>>(keys, N, n_keys, lb, R, bits, ntiles, tiles);
+    LAUNCH_CHECK();
+    stage(ctx, s, "owner:scan");
+    k_shard_scan_sums<<<nchunks, kShThreads, 0, s>>>(tiles, M, sums);
+    LAUNCH_CHECK();
+    k_shard_scan_top<<<1, kShThreads, 0, s>>>(sums, nchunks);
+    LAUNCH_CHECK();
+    k_shard_scan_apply<<<nchunks, kShThreads, 0, s>>>(tiles, M, sums);
+    LAUNCH_CHECK();
+    k_owner_totals<<<1, 64, 0, s>>>(tiles, N, n_keys, R, ntiles, counts);
+    LAUNCH_CHECK();
+    stage(ctx, s, "owner:scatter");
+    if (out_src)
+        k_owner_scatter<true><<<ntiles, kShThreads, 0, s>>>(keys, N, n_keys, lb, R, bits, ntiles,
+                                                            tiles, out_keys, out_src);
+    else
+        k_owner_scatter<false><<<ntiles, kShThreads, 0, s>>>(keys, N, n_keys, lb, R, bits, ntiles,
+                                                             tiles, out_keys, nullptr);
+    LAUNCH_CHECK();
+    stage(ctx, s, "owner:end");
     return st;
 }
 

@@ -15,7 +15,11 @@ Device pipeline per call (include/dpg.h):
   selection, whose columns join the noise kernel's.  A plan with VECTOR_SUM
   adds dpg_bound_records, dpg_vector_index and dpg_vector_sums behind the
   bounding and dpg_vector_clip_noise behind the selection; its D columns come
-  last.  The kept count reaches the host when the result's
+  last.  With several ranks the sorted tree keys, or the occupied partitions'
+summed rows, follow the partials to the partitions' owners
+(distributed.exchange_owner_keys: dpg_owner_split_keys, one more host
+synchronisation) and are merged there by dpg_sort_pairs_u64, or by
+dpg_vector_index and dpg_vector_sums.  The kept count reaches the host when the result's
   ids or values are first read (the one host synchronisation after the
   bounding), so a caller can enqueue the next release first.
 """
@@ -278,6 +282,52 @@ class DeviceAggregation:
         if not enc.pid_range_declared:  # a declared range is global; else the device reduces it
             enc.pid_min, enc.pid_count = 0, 0
 
+    def _own_quantile_keys(self, qkeys, n_qkeys, local_P: int, sptr):
+        """Several ranks: this rank's sorted tree keys pk << 16 | leaf go to
+        their partitions' owners (distributed.exchange_owner_keys: one split,
+        one host synchronisation, two collectives) and come back as
+        pk_local << 16 | leaf, one sorted run per source rank; a keys-only
+        sort merges the runs.  Returns the owned keys and their count on the
+        device, as dpg_quantiles reads them."""
+        backend = self.backend
+        dev = backend.device
+        got, _, total = distributed.exchange_owner_keys(
+            qkeys, n_qkeys, 16, backend.process_group, backend.ctx, sptr)
+        keys = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
+        backend.ctx.sort_pairs_u64(got.data_ptr(), None, total, 0,
+                                   16 + max(local_P - 1, 0).bit_length(), keys.data_ptr(), None,
+                                   sptr)
+        return keys, torch.tensor([total], dtype=torch.int64, device=dev)
+
+    def _own_vector_sums(self, rows, vsums, P: int, local_P: int, nnz_bound: int, sptr):
+        """Several ranks: the rows of this rank's occupied partitions (rows >
+        0, ascending: one fixed-size nonzero, the count stays on the device)
+        go to the partitions' owners with their partition id as key.  The
+        owner indexes the (pk_local, row) pairs it received -- source-rank
+        order, so a partition's rows are ascending by source rank -- and
+        adds them with dpg_vector_sums.  Returns the merged [local_P, D] sums
+        of the owned slice."""
+        backend = self.backend
+        ctx, dev = backend.ctx, backend.device
+        D = vsums.shape[1]
+        occ = rows > 0
+        n_occ = torch.count_nonzero(occ).reshape(1)
+        K = max(1, min(P, int(nnz_bound)))
+        idx = torch.nonzero_static(occ, size=K, fill_value=0).view(-1)
+        got, got_rows, total = distributed.exchange_owner_keys(
+            idx, n_occ, 0, backend.process_group, ctx, sptr, payload=vsums.index_select(0, idx))
+        merged = torch.empty((local_P, D), dtype=torch.float64, device=dev)
+        if local_P == 0:
+            return merged
+        keep_all = torch.ones(max(total, 1), dtype=torch.uint8, device=dev)
+        vkeys = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
+        n_vkeys = torch.empty(1, dtype=torch.int64, device=dev)
+        ctx.vector_index(_ptr(got), keep_all.data_ptr(), total, local_P, vkeys.data_ptr(),
+                         n_vkeys.data_ptr(), sptr)
+        ctx.vector_sums(vkeys.data_ptr(), n_vkeys.data_ptr(), _ptr(got_rows), total, D, local_P,
+                        merged.data_ptr(), sptr)
+        return merged
+
     def _run(self, gather: bool) -> DeviceResult:
         if _DROPPED:
             check_dropped()
@@ -298,11 +348,6 @@ class DeviceAggregation:
                       mean_const_value=0.0, msq_const_value=0.0))
         P = enc.n_partitions
         percentiles = self.plan is not None and bool(self.plan.percentiles)
-        if percentiles and backend.world_size > 1:
-            # on every rank, before any collective: the kept tree keys would
-            # have to move to their partitions' owners
-            raise NotImplementedError(
-                "percentiles are not built for multi-GPU releases (world_size > 1)")
         if backend.world_size > 1 and not enc.partitions_declared:
             # every rank must use the same dense partition ids and P, or the
             # exchange sums partials of different keys (or hangs)
@@ -310,11 +355,6 @@ class DeviceAggregation:
                 "multi-GPU aggregation needs globally dense integer partition ids: "
                 "pass ColumnarData(..., n_partitions=P) with pk in [0, P) on every rank")
         vector = self.plan.vector_size if self.plan is not None else None
-        if vector is not None and backend.world_size > 1:
-            # on every rank, before any collective: the kept rows would have
-            # to move to their partitions' owners
-            raise NotImplementedError(
-                "VECTOR_SUM is not built for multi-GPU releases (world_size > 1)")
         if vector is not None:
             # the reference's error class for a vector of another size
             if enc.value.dim() != 2 or tuple(enc.value.shape) != (enc.n, vector):
@@ -407,6 +447,14 @@ class DeviceAggregation:
                 if public_mask_local is not None:
                     public_mask_local = distributed.slice_bitmap(
                         enc.public_mask, pk_offset, pk_stride, local_P)
+                if percentiles:
+                    qkeys, n_qkeys = self._own_quantile_keys(qkeys, n_qkeys, local_P, sptr)
+                    qp = _native.fill(_native.QuantileParams,
+                                      dict(qfields, pk_offset=pk_offset, pk_stride=pk_stride,
+                                           nonce=nonce))
+                if vector is not None:
+                    vsums = self._own_vector_sums(rows, vsums, P, local_P, nnz_bound, sptr)
+                    self.last_vector_sums = vsums
             # this rank's merged partitions pk_offset + i * pk_stride, i < local_P
             self.last_slice = (tensors, pk_offset, pk_stride, local_P)
             lp = _native.Partials(local_P, tensors["rows"].data_ptr(),

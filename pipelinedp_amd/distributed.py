@@ -31,7 +31,12 @@ mode and `count` under `max_contributions` may differ from the one-process
 release; they equal the release of each rank's received records.
 
 With the records in place the only further exchange is the merge of the
-per-partition partials.
+per-partition partials -- and, for a plan with percentiles or VECTOR_SUM,
+of the kept items behind it: `exchange_owner_keys` sends partition-keyed
+items (sorted tree keys; the occupied partitions' summed rows) to the
+partitions' owners, ordered by one stable split on the device
+(dpg_owner_split_keys) whose R counts are read back: one more host
+synchronisation per release.
 
 Ownership is by partition key: rank r owns partitions r, r + R, r + 2R, ...
 (R ranks; `pk mod R`, the identity hash of the dense ids), at local index
@@ -146,11 +151,31 @@ def _exchange_column(send: torch.Tensor, in_splits, out_splits, group) -> torch.
     return recv.to(dev)
 
 
+def _split_sizes(counts: torch.Tensor, group, dev, what: str, items: str):
+    """ONE all_gather of this rank's R send counts (host int64[R]): every rank
+    then holds the R x R matrix [source, destination], so its own send and
+    receive splits; a receive total of 2^31 or more on any rank raises the
+    same ValueError on every rank."""
+    world = dist.get_world_size(group)
+    rank = dist.get_rank(group)
+    cdev = _coll_device(group, dev)
+    rows = [torch.empty(world, dtype=torch.int64, device=cdev) for _ in range(world)]
+    dist.all_gather(rows, counts.to(cdev), group=group)
+    matrix = torch.stack(rows).cpu()  # [source, destination]
+    worst = int(matrix.sum(0).max().item())
+    if worst >= 1 << 31:
+        raise ValueError(f"{what}: one rank would receive {worst} {items}; a rank "
+                         f"holds fewer than 2^31")
+    return matrix[rank].tolist(), matrix[:, rank].tolist()
+
+
 def shuffle_records(pid: torch.Tensor, pk: torch.Tensor, value: Optional[torch.Tensor], group,
                     ctx=None, stream=None):
     """Delivers every record to the rank `shard_of(pid, R)`; returns this
     rank's (pid, pk, value) in source-rank order, input order within a source
-    (value None stays None: every rank must pass None or none of them).
+    (value None stays None: every rank must pass None or none of them; a
+    [n, D] value -- VECTOR_SUM rows, D the same on every rank -- travels row
+    by row).
 
     Device tensors with the library context `ctx`: the send order is ONE
     stable split on the device (dpg_shard_records, stream-ordered on `stream`,
@@ -165,22 +190,28 @@ def shuffle_records(pid: torch.Tensor, pk: torch.Tensor, value: Optional[torch.T
     all ranks then raise the same ValueError), and one all_to_all_single per
     column.  The send buffers are freed column by column."""
     world = dist.get_world_size(group)
-    rank = dist.get_rank(group)
     dev = pid.device
     n = pid.numel()
     pid = pid.to(torch.int64).contiguous()
     pk = pk.to(torch.int64).contiguous()
     if value is not None:
         value = value.to(torch.float64).contiguous()
+    rows = value is not None and value.dim() == 2  # VECTOR_SUM: [n, D]
     if ctx is not None and dev.type == "cuda":
         s_pid, s_pk = torch.empty_like(pid), torch.empty_like(pk)
-        s_val = torch.empty_like(value) if value is not None else None
+        # the split moves one 8-byte value column: rows of vectors follow the
+        # record positions it moved in their place (exact in float64)
+        col = torch.arange(n, dtype=torch.float64, device=dev) if rows else value
+        s_val = torch.empty_like(col) if col is not None else None
         counts = torch.empty(world, dtype=torch.int64, device=dev)
         ctx.shard_records(pid.data_ptr(), pk.data_ptr(),
-                          value.data_ptr() if value is not None else None, n, world,
+                          col.data_ptr() if col is not None else None, n, world,
                           s_pid.data_ptr(), s_pk.data_ptr(),
                           s_val.data_ptr() if s_val is not None else None,
                           counts.data_ptr(), stream)
+        if rows:
+            s_val = value.index_select(0, s_val.to(torch.int64))
+        del col
         counts = counts.cpu()  # the one host synchronisation
     else:
         dest = shard_of(pid, world)
@@ -189,25 +220,89 @@ def shuffle_records(pid: torch.Tensor, pk: torch.Tensor, value: Optional[torch.T
         s_pid, s_pk = pid[order], pk[order]
         s_val = value[order] if value is not None else None
     del pid, pk, value
-    cdev = _coll_device(group, dev)
-    rows = [torch.empty(world, dtype=torch.int64, device=cdev) for _ in range(world)]
-    dist.all_gather(rows, counts.to(cdev), group=group)
-    matrix = torch.stack(rows).cpu()  # [source, destination]
-    worst = int(matrix.sum(0).max().item())
-    if worst >= 1 << 31:
-        raise ValueError(f"record shuffle: one rank would receive {worst} records; a rank "
-                         f"holds fewer than 2^31")
-    in_splits = matrix[rank].tolist()
-    out_splits = matrix[:, rank].tolist()
+    in_splits, out_splits = _split_sizes(counts, group, dev, "record shuffle", "records")
     r_pid = _exchange_column(s_pid, in_splits, out_splits, group)
     del s_pid
     r_pk = _exchange_column(s_pk, in_splits, out_splits, group)
     del s_pk
     r_val = None
-    if s_val is not None:
+    if s_val is not None and rows:
+        D = s_val.shape[1]
+        r_val = _exchange_column(s_val.view(-1), [c * D for c in in_splits],
+                                 [c * D for c in out_splits], group).view(-1, D)
+    elif s_val is not None:
         r_val = _exchange_column(s_val, in_splits, out_splits, group)
-        del s_val
+    del s_val
     return r_pid, r_pk, r_val
+
+
+def exchange_owner_keys(keys: torch.Tensor, n_keys, low_bits: int, group, ctx=None, stream=None,
+                        payload: Optional[torch.Tensor] = None):
+    """Delivers partition-keyed items to the rank that owns their partition.
+
+    keys: int64 tensor holding the 64-bit keys pk << low_bits | low; the first
+    n_keys of them count (a one-element int64 tensor -- on the keys' device,
+    so the count never reaches the host before the split -- an int, or None:
+    all).  Key k goes to rank `owner_of(pk)` = pk % R and arrives re-based to
+    the owner's local partition id: (pk // R) << low_bits | low.  payload: a
+    [n, D] float64 tensor (D the same on every rank; every rank passes one or
+    none does) whose row i travels with key i.
+
+    Returns (keys, payload or None, total): what this rank received, in
+    source-rank order, input order within a source, and its length.
+
+    Device tensors with the library context `ctx`: the send order is ONE
+    stable split on the device (dpg_owner_split_keys, stream-ordered on
+    `stream`, torch's current stream); reading its R counts back is the
+    exchange's one host synchronisation.  Host tensors (the gloo CPU tests,
+    no context): the same layout from a stable argsort of pk % R.
+
+    Every rank runs the same collectives whatever its local count, zero
+    included: one all_gather of the R counts (`_split_sizes`: a receive total
+    of 2^31 or more on any rank raises the same ValueError everywhere), one
+    all_to_all_single of the keys and, with a payload, a second one of its
+    rows gathered destination-major."""
+    world = dist.get_world_size(group)
+    dev = keys.device
+    keys = keys.to(torch.int64).contiguous().view(-1)
+    n_max = keys.numel()
+    if payload is not None:
+        payload = payload.to(torch.float64).contiguous()
+    if ctx is not None and dev.type == "cuda":
+        if not isinstance(n_keys, torch.Tensor):
+            n_keys = torch.tensor([n_max if n_keys is None else int(n_keys)], dtype=torch.int64,
+                                  device=dev)
+        s_keys = torch.empty_like(keys)
+        src = torch.empty(n_max, dtype=torch.int32, device=dev) if payload is not None else None
+        counts = torch.empty(world, dtype=torch.int64, device=dev)
+        ctx.owner_split_keys(keys.data_ptr(), n_keys.data_ptr(), n_max, int(low_bits), world,
+                             s_keys.data_ptr(), src.data_ptr() if src is not None else None,
+                             counts.data_ptr(), stream)
+        counts = counts.cpu()  # the one host synchronisation
+        sent = int(counts.sum().item())
+        s_keys = s_keys[:sent]
+        if src is not None:
+            src = src[:sent].to(torch.int64)  # positions < 2^31
+    else:
+        n = n_max if n_keys is None else int(n_keys)
+        keys = keys[:n]
+        # a logical shift: a key with bit 63 set is a negative int64
+        pk = (keys >> low_bits) & ((1 << (64 - low_bits)) - 1) if low_bits else keys
+        dest = pk % world
+        src = torch.argsort(dest, stable=True)
+        counts = torch.bincount(dest, minlength=world).cpu()
+        s_keys = (((pk // world) << low_bits) | (keys & ((1 << low_bits) - 1)))[src]
+    del keys
+    in_splits, out_splits = _split_sizes(counts, group, dev, "owner exchange", "keys")
+    r_keys = _exchange_column(s_keys, in_splits, out_splits, group)
+    del s_keys
+    r_pay = None
+    if payload is not None:
+        D = payload.shape[1]
+        rows = payload.index_select(0, src).view(-1)
+        r_pay = _exchange_column(rows, [c * D for c in in_splits], [c * D for c in out_splits],
+                                 group).view(-1, D)
+    return r_keys, r_pay, sum(out_splits)
 
 
 def _names(tensors) -> list:

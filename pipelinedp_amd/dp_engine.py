@@ -14,6 +14,7 @@ import torch
 
 from pipelinedp_amd import aggregate_params as agg
 from pipelinedp_amd import budget_accounting
+from pipelinedp_amd import columnar
 from pipelinedp_amd import combiners
 from pipelinedp_amd import data_extractors as dex
 from pipelinedp_amd import device_aggregate
@@ -222,7 +223,11 @@ class DPEngine:
             if bad:
                 raise NotImplementedError(
                     f"max_contributions is not supported for {bad}")
-        _check_col(col)
+        # one rank of a multi-GPU release may hold no records: it still takes
+        # part in every collective and owns its partitions
+        if not (isinstance(col, columnar.ColumnarData) and col.pk is not None
+                and getattr(self._backend, "world_size", 1) > 1):
+            _check_col(col)
         if params is None:
             raise ValueError("params must be set to a valid AggregateParams")
         if not isinstance(params, agg.AggregateParams):

@@ -221,14 +221,17 @@ class MI355XBackend(_HostCollectionOps, PipelineBackend):
         Partition pk is owned by rank pk mod world_size.
       percentiles: opt in to Metrics.PERCENTILE.  Off
         by default, where DPEngine.aggregate raises NotImplementedError for
-        them as before: the route costs about 12 times the tuned bounding,
-        runs on one GPU only, and its parity with PyDP's QuantileTree is
-        pinned to a restatement, not to PyDP.
+        them as before: the route costs about 12 times the tuned bounding
+        (with a process group also one more host synchronisation: the kept
+        tree keys move to their partitions' owners), and its parity with
+        PyDP's QuantileTree is pinned to a restatement, not to PyDP.
       vector_sums: opt in to Metrics.VECTOR_SUM.  Off
         by default, where DPEngine.aggregate raises NotImplementedError for it
-        as before: the route sorts the kept records once more, runs on one
-        GPU only, and its noise scale is the reference's calibration
-        (eps / D per coordinate, vector_max_norm not in it), reproduced.
+        as before: the route sorts the kept records once more (with a process
+        group the occupied partitions' summed rows move to their owners: one
+        more host synchronisation), and its noise scale is the reference's
+        calibration (eps / D per coordinate, vector_max_norm not in it),
+        reproduced.
     """
 
     def __init__(self, device: Optional[int] = None, seed: Optional[int] = None,
