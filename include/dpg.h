@@ -479,6 +479,54 @@ int dpg_owner_split_keys(dpg_ctx *ctx, const uint64_t *keys, const int64_t *n_ke
                          uint64_t *out_keys, uint32_t *out_src, int64_t *counts,
                          void *stream);
 
+/* ---- multi-GPU utility analysis: pairs to the rank that owns their partition ----
+ * The per-partition utility combiners need every (privacy id, partition) pair
+ * of a partition on one rank, so each rank's pre-aggregate travels to the
+ * partitions' owners between dpg_preaggregate and dpg_utility_analysis
+ * (distributed.exchange_owner_pairs; csrc/dpg_pairx.h).
+ *
+ * Stable split of pairs[0, n) (device; n is a host count, as dpg_preaggregate
+ * returned it) by owner = pk % nranks (1 <= nranks <= DPG_SHARD_MAX_RANKS).
+ * out_pairs (device, n entries, not overlapping pairs) is destination-major,
+ * in input order within a destination: the pairs of destination d occupy
+ * [sum(counts[0..d)), +counts[d]).  Every entry's pk is rewritten to
+ * pk / nranks; its other 20 bytes -- the leader bit and the bits of sum
+ * included -- are carried unchanged.  counts is a device int64[nranks].
+ * n == 0 gives all-zero counts (the pair pointers may then be NULL).  nranks
+ * out of range, n < 0, a NULL counts or (n > 0) pairs / out_pairs:
+ * DPG_ERR_INVALID_ARG; n >= 2^31: DPG_ERR_UNSUPPORTED; both before any device
+ * work.  Stream-ordered, no host synchronisation. */
+int dpg_owner_split_pairs(dpg_ctx *ctx, const dpg_pair_entry *pairs, int64_t n, int nranks,
+                          dpg_pair_entry *out_pairs, int64_t *counts, void *stream);
+
+/* Merge of pk-sorted runs into one pre-aggregate.  pairs (device) holds nruns
+ * consecutive runs (1 <= nruns <= DPG_SHARD_MAX_RANKS); run r is
+ * [run_start[r], run_start[r + 1]) (host int64[nruns + 1], run_start[0] = 0,
+ * ascending, n = run_start[nruns] < 2^31), each ascending by pk.  out_pairs
+ * (device, n entries, not overlapping pairs) receives them ascending by pk
+ * and, within a partition, by run and then by position in the run: a fixed
+ * order, the same on every execution.  partition_start (device
+ * int64[n_partitions + 1]) is written as dpg_preaggregate writes it.  A
+ * counting placement, not a sort: O(n + nruns * n_partitions) work, integer
+ * only; nruns * n_partitions < 2^32 - 1 (else DPG_ERR_UNSUPPORTED, as n >=
+ * 2^31).
+ * *n_bad (device int64) counts the entries with pk >= n_partitions or with a
+ * pk below that of an in-range predecessor in their run.  They are never
+ * written.  *n_bad == 0 if and only if every run is in range and ascending.
+ * The other entries are placed as if the bad ones were absent when every bad
+ * entry sits between entries of two different partitions (or at an end of its
+ * run) and the runs without the bad entries are ascending; otherwise their
+ * places, always inside out_pairs, are unspecified and slots may stay
+ * unwritten.  Whatever the input, partition_start is ascending and
+ * partition_start[n_partitions] <= n, so a reader of the result stays inside
+ * out_pairs.
+ * Empty runs, n == 0 (the pair pointers may then be NULL) and nruns == 1 (a
+ * copy and the starts) are valid.  Bad arguments: DPG_ERR_INVALID_ARG before
+ * any device work.  Stream-ordered, no host synchronisation. */
+int dpg_merge_pair_runs(dpg_ctx *ctx, const dpg_pair_entry *pairs, const int64_t *run_start,
+                        int nruns, int64_t n_partitions, dpg_pair_entry *out_pairs,
+                        int64_t *partition_start, int64_t *n_bad, void *stream);
+
 /* ---- percentiles: kept records, quantile tree (combiners.py:532-611) ----
  * Stable LSD radix sort of n (key, payload) pairs by the key bits
  * [begin_bit, end_bit) (0 <= begin_bit <= end_bit <= 64), 8 bits per pass;
@@ -592,8 +640,11 @@ int dpg_vector_clip_noise(dpg_ctx *ctx, const double *sums, int64_t n_partitions
 /* Timing/profiling aid: per-stage device time (ms) of the last
  * dpg_bound_aggregate / dpg_preaggregate / dpg_dataset_histograms /
  * dpg_bound_records / dpg_quantile_keys / dpg_vector_index / dpg_vector_sums
- * / dpg_owner_split_keys call ("vector:keys", "vector:sort:...", "vector:sum",
- * "vector:merge"; "owner:count", "owner:scan", "owner:scatter"),
+ * / dpg_owner_split_keys / dpg_owner_split_pairs / dpg_merge_pair_runs call
+ * ("vector:keys", "vector:sort:...", "vector:sum", "vector:merge";
+ * "owner:count", "owner:scan", "owner:scatter"; "pairs:count", "pairs:scan",
+ * "pairs:owner_split" (the split's scatter kernel); "pairs:bounds",
+ * "pairs:scan", "pairs:merge" (the merge's placement kernel)),
  * measured with HIP events on its stream (waits for the last event).
  * names (comma separated, <= names_len bytes): e.g. "begin",
  * "partition1:hist", "partition1:scatter", "partition2:hist",

@@ -23,7 +23,8 @@ EXPORTED = ("dpg_ctx_create", "dpg_ctx_destroy", "dpg_last_error", "dpg_set_seed
             "dpg_comm_unique_id", "dpg_ctx_create_comm", "dpg_reduce_scatter_partials",
             "dpg_pack_partials", "dpg_unpack_partials", "dpg_export_error",
             "dpg_import_error", "dpg_shard_records", "dpg_check_shard",
-            "dpg_owner_split_keys", "dpg_sort_pairs_u64", "dpg_bound_records", "dpg_quantile_keys", "dpg_quantiles",
+            "dpg_owner_split_keys", "dpg_owner_split_pairs", "dpg_merge_pair_runs",
+            "dpg_sort_pairs_u64", "dpg_bound_records", "dpg_quantile_keys", "dpg_quantiles",
             "dpg_vector_index", "dpg_vector_sums", "dpg_vector_clip_noise")
 
 COMM_ID_BYTES = 128  # DPG_COMM_ID_BYTES
@@ -237,6 +238,11 @@ def load():
         lib.dpg_check_shard.restype = ctypes.c_int
         lib.dpg_owner_split_keys.argtypes = [vp, vp, vp, i64, i32, ctypes.c_int, vp, vp, vp, vp]
         lib.dpg_owner_split_keys.restype = ctypes.c_int
+        lib.dpg_owner_split_pairs.argtypes = [vp, vp, i64, ctypes.c_int, vp, vp, vp]
+        lib.dpg_owner_split_pairs.restype = ctypes.c_int
+        lib.dpg_merge_pair_runs.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
+                                            i64, vp, vp, vp, vp]
+        lib.dpg_merge_pair_runs.restype = ctypes.c_int
         lib.dpg_sort_pairs_u64.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
         lib.dpg_sort_pairs_u64.restype = ctypes.c_int
         lib.dpg_bound_records.argtypes = [vp, vp, vp, i64, ctypes.POINTER(BoundParams), vp, vp]
@@ -372,6 +378,26 @@ class Context:
         st = self.lib.dpg_owner_split_keys(self.handle, keys_ptr, n_keys_ptr, n_max, low_bits,
                                            nranks, out_keys_ptr, out_src_ptr, counts_ptr, stream)
         self.check(st, "dpg_owner_split_keys")
+
+    def owner_split_pairs(self, pairs_ptr, n, nranks, out_pairs_ptr, counts_ptr, stream):
+        """Stable split of n dpg_pair_entry by the owner pk % nranks into
+        out_pairs, destination-major, pk re-based to the owner's local
+        partition ids (pk // nranks); counts (device int64[nranks])."""
+        st = self.lib.dpg_owner_split_pairs(self.handle, pairs_ptr, n, nranks, out_pairs_ptr,
+                                            counts_ptr, stream)
+        self.check(st, "dpg_owner_split_pairs")
+
+    def merge_pair_runs(self, pairs_ptr, run_start, n_partitions, out_pairs_ptr, starts_ptr,
+                        n_bad_ptr, stream):
+        """Merges the pk-sorted runs [run_start[r], run_start[r + 1]) (host
+        ints) of dpg_pair_entry into out_pairs, ascending by pk, then run,
+        then position; starts (device int64[n_partitions + 1]); the device
+        int64 at n_bad_ptr counts out-of-range and descending entries."""
+        rs = (ctypes.c_int64 * len(run_start))(*[int(x) for x in run_start])
+        st = self.lib.dpg_merge_pair_runs(self.handle, pairs_ptr, rs, len(run_start) - 1,
+                                          n_partitions, out_pairs_ptr, starts_ptr, n_bad_ptr,
+                                          stream)
+        self.check(st, "dpg_merge_pair_runs")
 
     def sort_pairs_u64(self, keys_in_ptr, vals_in_ptr, n, begin_bit, end_bit, keys_out_ptr,
                        vals_out_ptr, stream):

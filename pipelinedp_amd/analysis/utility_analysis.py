@@ -35,6 +35,7 @@ from pipelinedp_amd import aggregate_params as agg
 from pipelinedp_amd import budget_accounting
 from pipelinedp_amd import columnar
 from pipelinedp_amd import data_extractors as dex
+from pipelinedp_amd import distributed
 from pipelinedp_amd import dp_computations as dpc
 from pipelinedp_amd import partition_selection
 from pipelinedp_amd import pipeline_backend
@@ -128,6 +129,10 @@ class UtilityAnalysis:
         _check_options(options, data_extractors)
         if not isinstance(backend, pipeline_backend.MI355XBackend):
             raise NotImplementedError("utility analysis runs on MI355XBackend only")
+        if options.pre_aggregated_data:
+            # pre-aggregated rows carry no privacy ids to shard by
+            pipeline_backend.require_one_process(
+                backend, "utility analysis of pre-aggregated data (options.pre_aggregated_data)")
         self.col = col
         self.backend = backend
         self.options = options
@@ -180,14 +185,25 @@ class UtilityAnalysis:
             ps = pre_aggregation.device_pairs(self.col, self.extractors, self.backend,
                                               self.public, dev)
         self.n_pairs = ps.n_pairs
+        # several ranks: this rank's owned slice (lo, stride, n) of the dense
+        # ids, analysed under local ids; n_bad: what the pair exchange dropped
+        self.owned, self._n_bad = ps.owned, ps.n_bad
         return ps.pairs, ps.starts, ps.n_partitions, ps.key_table, ps.public_mask
+
+    def _global_ids(self, ids: np.ndarray) -> np.ndarray:
+        """Dense ids of this run's (local) partition ids."""
+        if self.owned is None:
+            return ids
+        lo, stride, _ = self.owned
+        return lo + ids * stride
 
     def _sample_mask(self, P, key_table, dev):
         prob = self.options.partitions_sampling_prob
         if prob >= 1:
             return None
         bound = _sample_bound(prob)
-        keys = columnar.decode_keys(np.arange(P), key_table)
+        # several ranks: the hash of the global keys of the owned ids only
+        keys = columnar.decode_keys(self._global_ids(np.arange(P)), key_table)
         keep = np.array([_keep_by_hash(k, bound) for k in keys], bool)
         self.sampled = keep
         return torch.from_numpy(np.packbits(keep, bitorder="little")).to(dev)
@@ -232,7 +248,10 @@ class UtilityAnalysis:
         rep = torch.empty((len(BUCKET_BOUNDS), F, C), **f64)
         # one device pass per 64 configurations (lane = configuration); the
         # pre-aggregate is shared, the outputs are stitched along C
-        for c0 in range(0, C, 64):
+        if P == 0:  # a rank that owns no partition adds nothing to the report
+            rep.zero_()
+            self.n_out = 0
+        for c0 in range(0, C if P > 0 else 0, 64):
             c1 = min(C, c0 + 64)
             whole = c0 == 0 and c1 == C
             up = _native.UaParams()
@@ -257,11 +276,31 @@ class UtilityAnalysis:
                 rep[..., c0:c1] = r_c
                 if keep is not None:
                     keep[:, c0:c1] = k_c
+        self.stage_ms = ctx.stage_times()
+        if self.owned is not None:
+            rep = self._sum_reports(rep)
         self.pairs, self.starts, self.key_table = pairs, starts, key_table
         self.sample, self.pub_mask = sample, pub_mask
         self.raw_all, self.err_all, self.keep_all, self.rep = raw, err, keep, rep
-        self.stage_ms = ctx.stage_times()
         self._done = True
+
+    def _sum_reports(self, rep: torch.Tensor) -> torch.Tensor:
+        """Several ranks: ONE all_reduce sums the report fields of every
+        rank's owned partitions (each is a sum over partitions) and, in the
+        same buffer, the entries the pair exchange dropped; a nonzero total
+        raises on every rank together."""
+        group = self.backend.process_group
+        buf = torch.cat([rep.reshape(-1), self._n_bad.to(torch.float64)])
+        host = not distributed._is_nccl(group)
+        if host:
+            buf = buf.cpu()
+        torch.distributed.all_reduce(buf, op=torch.distributed.ReduceOp.SUM, group=group)
+        n_bad = int(buf[-1].item())
+        if n_bad:
+            raise RuntimeError(
+                f"utility analysis: {n_bad} pre-aggregate entries reached a rank out of order "
+                f"or outside its partitions (ranks disagree on n_partitions or world size?)")
+        return buf[:-1].to(rep.device).view(rep.shape)
 
     def output_ids(self) -> torch.Tensor:
         """Dense ids of the result's partitions: the public ones, or those
@@ -373,7 +412,7 @@ class UtilityAnalysis:
         (utility_analysis.py:86-100)."""
         self.run()
         ids = self.output_ids()
-        keys = columnar.decode_keys(ids.cpu().numpy(), self.key_table)
+        keys = columnar.decode_keys(self._global_ids(ids.cpu().numpy()), self.key_table)
         std = {m: [cf.noise_std[m] for cf in self.configs] for m in self.metrics}
         C = len(self.configs)
         M = len(self.metrics)

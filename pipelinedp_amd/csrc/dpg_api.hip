@@ -68,6 +68,7 @@ static hipError_t set_func_attr(const void *kern, hipFuncAttribute attr, int val
 #include "dpg_common.h"
 #include "dpg_hist.h"
 #include "dpg_owner.h"
+#include "dpg_pairx.h"
 #include "dpg_partition.h"
 #include "dpg_quantile.h"
 #include "dpg_records.h"
@@ -2849,6 +2850,130 @@ int dpg_owner_split_keys(dpg_ctx *ctx, const uint64_t *keys, const int64_t *n_ke
                                                              tiles, out_keys, nullptr);
     LAUNCH_CHECK();
     stage(ctx, s, "owner:end");
+    return st;
+}
+
+static bool ranges_overlap(const void *a, const void *b, size_t bytes);
+
+int dpg_owner_split_pairs(dpg_ctx *ctx, const dpg_pair_entry *pairs, int64_t n, int nranks,
+                          dpg_pair_entry *out_pairs, int64_t *counts, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (nranks < 1 || nranks > DPG_SHARD_MAX_RANKS)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "nranks must be in [1, DPG_SHARD_MAX_RANKS]");
+    if (n < 0 || !counts) return fail(ctx, DPG_ERR_INVALID_ARG, "n < 0 or counts is NULL");
+    if (n >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n must be < 2^31 per device");
+    // n == 0 reads and writes no pair: the pair pointers may be anything
+    if (n > 0 && (!pairs || !out_pairs))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "pairs and out_pairs must be given");
+    if (n > 0 && ranges_overlap(pairs, out_pairs, (size_t)n * sizeof(dpg_pair_entry)))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "out_pairs must not overlap pairs");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int st = DPG_OK;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(counts, 0, (size_t)nranks * 8, s));
+        return st;
+    }
+    ctx->stage_names.clear();
+    ctx->n_events_used = 0;
+    ctx->last_stream = s;
+    const uint32_t R = (uint32_t)nranks, N = (uint32_t)n;
+    uint32_t bits = 0;
+    while ((1u << bits) < R) ++bits;
+    const uint32_t ntiles = (N + DPG_SHARD_TILE - 1) / DPG_SHARD_TILE;
+    const uint32_t M = R * ntiles;  // <= 64 * 2^20
+    const uint32_t nchunks = (M + kScanChunk - 1) / kScanChunk;
+    const ItemPA *in = reinterpret_cast<const ItemPA *>(pairs);
+    WS(tiles, uint32_t, "pairx.tiles", M);
+    WS(sums, uint32_t, "pairx.sums", nchunks);
+    stage(ctx, s, "pairs:count");
+    k_pairx_count<<<ntiles, kShThreads, 0, s>>>(in, N, R, bits, ntiles, tiles);
+    LAUNCH_CHECK();
+    stage(ctx, s, "pairs:scan");
+    k_shard_scan_sums<<<nchunks, kShThreads, 0, s>>>(tiles, M, sums);
+    LAUNCH_CHECK();
+    k_shard_scan_top<<<1, kShThreads, 0, s>>>(sums, nchunks);
+    LAUNCH_CHECK();
+    k_shard_scan_apply<<<nchunks, kShThreads, 0, s>>>(tiles, M, sums);
+    LAUNCH_CHECK();
+    k_shard_totals<<<1, 64, 0, s>>>(tiles, N, R, ntiles, counts);
+    LAUNCH_CHECK();
+    stage(ctx, s, "pairs:owner_split");
+    k_pairx_scatter<<<ntiles, kShThreads, 0, s>>>(in, N, R, bits, ntiles, tiles,
+                                                  reinterpret_cast<ItemPA *>(out_pairs));
+    LAUNCH_CHECK();
+    stage(ctx, s, "pairs:end");
+    return st;
+}
+
+int dpg_merge_pair_runs(dpg_ctx *ctx, const dpg_pair_entry *pairs, const int64_t *run_start,
+                        int nruns, int64_t n_partitions, dpg_pair_entry *out_pairs,
+                        int64_t *partition_start, int64_t *n_bad, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (nruns < 1 || nruns > DPG_SHARD_MAX_RANKS)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "nruns must be in [1, DPG_SHARD_MAX_RANKS]");
+    if (!run_start || n_partitions < 0 || !partition_start || !n_bad)
+        return fail(ctx, DPG_ERR_INVALID_ARG,
+                    "n_partitions < 0, or run_start, partition_start or n_bad is NULL");
+    if (run_start[0] != 0)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "run_start[0] must be 0");
+    for (int r = 0; r < nruns; ++r)
+        if (run_start[r + 1] < run_start[r])
+            return fail(ctx, DPG_ERR_INVALID_ARG, "run_start must be ascending");
+    const int64_t n = run_start[nruns];
+    if (n >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n must be < 2^31 per device");
+    // the scan counts (partition, run) segments with 32-bit indices
+    if (n_partitions * nruns >= 0xFFFFFFFFll)
+        return fail(ctx, DPG_ERR_UNSUPPORTED, "nruns * n_partitions must be < 2^32 - 1");
+    if (n > 0 && (!pairs || !out_pairs))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "pairs and out_pairs must be given");
+    if (n > 0 && ranges_overlap(pairs, out_pairs, (size_t)n * sizeof(dpg_pair_entry)))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "out_pairs must not overlap pairs");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int st = DPG_OK;
+    HIP_TRY(hipMemsetAsync(n_bad, 0, 8, s));
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(partition_start, 0, (size_t)(n_partitions + 1) * 8, s));
+        return st;
+    }
+    ctx->stage_names.clear();
+    ctx->n_events_used = 0;
+    ctx->last_stream = s;
+    PairRuns rs;
+    rs.nruns = (uint32_t)nruns;
+    for (int r = 0; r <= nruns; ++r) rs.start[r] = (uint32_t)run_start[r];
+    const uint32_t N = (uint32_t)n, P = (uint32_t)n_partitions;
+    const uint32_t M = P * (uint32_t)nruns + 1u;  // one more: the scan leaves the total there
+    const uint32_t nchunks = (M + kScanChunk - 1) / kScanChunk;
+    const ItemPA *in = reinterpret_cast<const ItemPA *>(pairs);
+    WS(cnt, uint32_t, "pairx.cnt", M);
+    WS(first, uint32_t, "pairx.first", M);
+    WS(sums, uint32_t, "pairx.sums", nchunks);
+    const unsigned blocks = (unsigned)std::min<int64_t>((n + kShThreads - 1) / kShThreads,
+                                                        (int64_t)ctx->n_cu * 8);
+    stage(ctx, s, "pairs:bounds");
+    HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)M * 4, s));
+    k_pairx_bounds<<<blocks, kShThreads, 0, s>>>(in, rs, N, P, cnt, first,
+                                                 reinterpret_cast<unsigned long long *>(n_bad));
+    LAUNCH_CHECK();
+    stage(ctx, s, "pairs:scan");
+    k_shard_scan_sums<<<nchunks, kShThreads, 0, s>>>(cnt, M, sums);
+    LAUNCH_CHECK();
+    k_shard_scan_top<<<1, kShThreads, 0, s>>>(sums, nchunks);
+    LAUNCH_CHECK();
+    k_shard_scan_apply<<<nchunks, kShThreads, 0, s>>>(cnt, M, sums);
+    LAUNCH_CHECK();
+    const unsigned sblocks = (unsigned)std::min<int64_t>((n_partitions + kShThreads) / kShThreads,
+                                                         (int64_t)ctx->n_cu * 8);
+    k_pairx_starts<<<sblocks, kShThreads, 0, s>>>(cnt, (uint32_t)nruns, n_partitions,
+                                                  partition_start);
+    LAUNCH_CHECK();
+    stage(ctx, s, "pairs:merge");
+    k_pairx_place<<<blocks, kShThreads, 0, s>>>(in, rs, N, P, cnt, first,
+                                                reinterpret_cast<ItemPA *>(out_pairs));
+    LAUNCH_CHECK();
+    stage(ctx, s, "pairs:end");
     return st;
 }
 

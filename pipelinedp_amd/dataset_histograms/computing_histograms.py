@@ -135,6 +135,7 @@ def compute_dataset_histograms(col, data_extractors: dex.DataExtractors, backend
     """1-element collection with the DatasetHistograms of the rows
     (computing_histograms.py:420-474)."""
     _require_device_backend(backend)
+    pipeline_backend.require_one_process(backend, "compute_dataset_histograms")
 
     def run():
         ps = pre_aggregation.device_pairs(col, data_extractors, backend, None, backend.device)
@@ -149,6 +150,8 @@ def compute_dataset_histograms_on_preaggregated_data(
     (partition key, (count, sum, n_partitions, n_contributions))
     (computing_histograms.py:642-684)."""
     _require_device_backend(backend)
+    pipeline_backend.require_one_process(backend,
+                                         "compute_dataset_histograms_on_preaggregated_data")
 
     def run():
         ps = pre_aggregation.host_preaggregated_pairs(col, data_extractors, None, backend.device)

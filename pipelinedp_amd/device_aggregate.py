@@ -252,35 +252,10 @@ class DeviceAggregation:
         this rank owns every privacy id it holds (one kernel, one all_reduce;
         every rank raises when any rank fails), 'shuffle' sends every record
         to its owner (distributed.shuffle_records) and bounds what arrives."""
-        backend = self.backend
         mode = self.col.sharding if isinstance(self.col, columnar.ColumnarData) else "trusted"
-        if backend.world_size <= 1 or mode == "trusted" or self.bounds_already_enforced:
+        if self.bounds_already_enforced:
             return
-        if not enc.pid_unencoded:
-            # the column's type is the same on every rank, so every rank raises
-            raise ValueError(
-                f"sharding={mode!r} needs integer privacy ids spanning at most 2^32 values: a "
-                f"per-rank dictionary encoding of other ids is not consistent across ranks")
-        dev, group = backend.device, backend.process_group
-        with torch.cuda.device(dev):
-            sptr = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            if mode == "verify":
-                n_bad = torch.empty(1, dtype=torch.int64, device=dev)
-                backend.ctx.check_shard(_ptr(enc.pid), enc.n, backend.world_size,
-                                        torch.distributed.get_rank(group), n_bad.data_ptr(), sptr)
-                # no rank raises before the collective
-                total = distributed.sum_over_ranks(n_bad, group)
-                if total:
-                    raise ValueError(
-                        f"sharding='verify': {total} records are on a rank that does not own "
-                        f"their privacy id (distributed.shard_of); use sharding='shuffle'")
-                return
-            enc.pid, enc.pk, enc.value = distributed.shuffle_records(
-                enc.pid, enc.pk, enc.value, group, backend.ctx, sptr)
-        enc.n = int(enc.pk.numel())
-        enc.rec_id_offset = 0
-        if not enc.pid_range_declared:  # a declared range is global; else the device reduces it
-            enc.pid_min, enc.pid_count = 0, 0
+        distributed.place_records(enc, self.backend, mode)
 
     def _own_quantile_keys(self, qkeys, n_qkeys, local_P: int, sptr):
         """Several ranks: this rank's sorted tree keys pk << 16 | leaf go to
@@ -351,9 +326,7 @@ class DeviceAggregation:
         if backend.world_size > 1 and not enc.partitions_declared:
             # every rank must use the same dense partition ids and P, or the
             # exchange sums partials of different keys (or hangs)
-            raise ValueError(
-                "multi-GPU aggregation needs globally dense integer partition ids: "
-                "pass ColumnarData(..., n_partitions=P) with pk in [0, P) on every rank")
+            raise ValueError(distributed.DENSE_IDS_ERROR)
         vector = self.plan.vector_size if self.plan is not None else None
         if vector is not None:
             # the reference's error class for a vector of another size

@@ -38,6 +38,14 @@ partitions' owners, ordered by one stable split on the device
 (dpg_owner_split_keys) whose R counts are read back: one more host
 synchronisation per release.
 
+The utility analysis moves whole pre-aggregate entries the same way:
+`exchange_owner_pairs` splits a rank's pk-sorted (privacy id, partition) pairs
+by owner (dpg_owner_split_pairs), sends them in ONE all_to_all and merges the
+R sorted runs it receives into the owned slice's pre-aggregate
+(dpg_merge_pair_runs).  The per-partition utility combiners are not sums over
+ranks -- the selection probability is a convolution over a partition's pairs
+-- so the pairs, not partials, have to meet.
+
 Ownership is by partition key: rank r owns partitions r, r + R, r + 2R, ...
 (R ranks; `pk mod R`, the identity hash of the dense ids), at local index
 pk // R.  Interleaving spreads hot low ids -- an unpermuted Zipf key space
@@ -75,6 +83,7 @@ with global partition ids -- never by rank -- and the release nonce comes
 from rank 0, so the selected-partition set is identical for any world size
 (SURVEY.md 8(e)).
 """
+import ctypes
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -303,6 +312,146 @@ def exchange_owner_keys(keys: torch.Tensor, n_keys, low_bits: int, group, ctx=No
         r_pay = _exchange_column(rows, [c * D for c in in_splits], [c * D for c in out_splits],
                                  group).view(-1, D)
     return r_keys, r_pay, sum(out_splits)
+
+
+DENSE_IDS_ERROR = ("multi-GPU aggregation needs globally dense integer partition ids: "
+                   "pass ColumnarData(..., n_partitions=P) with pk in [0, P) on every rank")
+
+
+def place_records(enc, backend, mode: str) -> None:
+    """ColumnarData(sharding=mode) with several ranks, applied to the encoded
+    input `enc` in place before bounding or pre-aggregation: 'trusted' does
+    nothing, 'verify' checks that this rank owns every privacy id it holds
+    (one kernel, one all_reduce; every rank raises when any rank fails),
+    'shuffle' sends every record to its owner (shuffle_records) and leaves
+    what arrives, with record id offset 0."""
+    if backend.world_size <= 1 or mode == "trusted":
+        return
+    if not enc.pid_unencoded:
+        # the column's type is the same on every rank, so every rank raises
+        raise ValueError(
+            f"sharding={mode!r} needs integer privacy ids spanning at most 2^32 values: a "
+            f"per-rank dictionary encoding of other ids is not consistent across ranks")
+    dev, group = backend.device, backend.process_group
+    with torch.cuda.device(dev):
+        sptr = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if mode == "verify":
+            n_bad = torch.empty(1, dtype=torch.int64, device=dev)
+            backend.ctx.check_shard(ctypes.c_void_p(enc.pid.data_ptr()), enc.n,
+                                    backend.world_size, dist.get_rank(group), n_bad.data_ptr(),
+                                    sptr)
+            # no rank raises before the collective
+            total = sum_over_ranks(n_bad, group)
+            if total:
+                raise ValueError(
+                    f"sharding='verify': {total} records are on a rank that does not own "
+                    f"their privacy id (distributed.shard_of); use sharding='shuffle'")
+            return
+        enc.pid, enc.pk, enc.value = shuffle_records(enc.pid, enc.pk, enc.value, group,
+                                                     backend.ctx, sptr)
+    enc.n = int(enc.pk.numel())
+    enc.rec_id_offset = 0
+    if not enc.pid_range_declared:  # a declared range is global; else the device reduces it
+        enc.pid_min, enc.pid_count = 0, 0
+
+
+def exchange_owner_pairs(pairs: torch.Tensor, n_pairs: int, P: int, group, ctx=None,
+                         stream=None):
+    """Delivers the entries of a pk-sorted pre-aggregate to the ranks that own
+    their partitions and merges what arrives.
+
+    pairs: float64 [cap, 3] tensor viewed as 24-byte dpg_pair_entry, the first
+    n_pairs of them ascending by pk (as dpg_preaggregate writes them) with pk
+    the global dense id in [0, P).  The entry of partition pk goes to rank
+    pk % R and arrives with pk re-based to the owner's local id pk // R; its
+    other 20 bytes travel unchanged.
+
+    Returns (pairs, starts, n_local, n, n_bad): this rank's owned slice as a
+    pre-aggregate -- the received entries ascending by local pk and, within a
+    partition, by source rank and then by the source's order; starts
+    (int64[n_local + 1]) delimiting the partitions; n_local =
+    owned(P, R, rank)[2]; the number of entries n; and n_bad, a one-element
+    int64 tensor counting received entries that were out of range or out of
+    order (nonzero only if a sender broke the contract: such entries are
+    dropped, and the caller is expected to fail on every rank).
+
+    Device tensors with the library context `ctx`: ONE stable split on the
+    device (dpg_owner_split_pairs) and one merge of the received runs
+    (dpg_merge_pair_runs), stream-ordered on `stream` (torch's current
+    stream); reading the split's R counts back is the exchange's one host
+    synchronisation.  Host tensors (the gloo CPU tests, no context): the same
+    layout from a stable argsort of pk % R and, for the merge, of the received
+    local pk.
+
+    Every rank runs the same collectives whatever it holds, nothing included:
+    one all_gather of the R counts (`_split_sizes`: a receive total of 2^31 or
+    more on any rank raises the same ValueError everywhere) and one
+    all_to_all_single of the entries as float64 words (splits x 3).  The send
+    buffer is freed before the merge."""
+    world = dist.get_world_size(group)
+    rank = dist.get_rank(group)
+    dev = pairs.device
+    n = int(n_pairs)
+    n_local = owned(P, world, rank)[2]
+    pairs = pairs.contiguous().view(-1, 3)
+    on_device = ctx is not None and dev.type == "cuda"
+    if on_device:
+        send = torch.empty((max(n, 1), 3), dtype=torch.float64, device=dev)
+        counts = torch.empty(world, dtype=torch.int64, device=dev)
+        ctx.owner_split_pairs(pairs.data_ptr(), n, world, send.data_ptr(), counts.data_ptr(),
+                              stream)
+        counts = counts.cpu()  # the one host synchronisation
+        send = send[:n]
+    else:
+        send = pairs[:n].clone()
+        pk = _pair_pk(send)
+        dest = pk % world
+        order = torch.argsort(dest, stable=True)
+        counts = torch.bincount(dest, minlength=world).cpu()
+        _set_pair_pk(send, pk // world)
+        send = send[order]
+    del pairs
+    in_splits, out_splits = _split_sizes(counts, group, dev, "pair exchange", "pairs")
+    recv = _exchange_column(send.reshape(-1), [3 * c for c in in_splits],
+                            [3 * c for c in out_splits], group).view(-1, 3)
+    del send
+    total = sum(out_splits)
+    if on_device:
+        run_start = [0]
+        for c in out_splits:
+            run_start.append(run_start[-1] + c)
+        merged = torch.empty((max(total, 1), 3), dtype=torch.float64, device=dev)
+        starts = torch.empty(n_local + 1, dtype=torch.int64, device=dev)
+        n_bad = torch.empty(1, dtype=torch.int64, device=dev)
+        ctx.merge_pair_runs(recv.data_ptr(), run_start, n_local, merged.data_ptr(),
+                            starts.data_ptr(), n_bad.data_ptr(), stream)
+        return merged, starts, n_local, total, n_bad
+    pk = _pair_pk(recv)
+    run = torch.repeat_interleave(torch.arange(world), torch.tensor(out_splits))
+    # bad as dpg_merge_pair_runs defines it: out of range, or below an
+    # in-range predecessor of the same run
+    prev_ok = torch.zeros(total, dtype=torch.bool)
+    if total > 1:
+        prev_ok[1:] = (run[1:] == run[:-1]) & (pk[:-1] < n_local)
+    bad = pk >= n_local
+    if total > 1:
+        bad[1:] |= prev_ok[1:] & (pk[1:] < pk[:-1])
+    keep = torch.nonzero(~bad).flatten()
+    order = keep[torch.argsort(pk[keep], stable=True)]
+    merged = recv[order]
+    starts = torch.searchsorted(pk[order].contiguous(), torch.arange(n_local + 1))
+    return (merged.to(dev), starts.to(torch.int64).to(dev), n_local, int(order.numel()),
+            bad.sum().reshape(1).to(torch.int64).to(dev))
+
+
+def _pair_pk(pairs: torch.Tensor) -> torch.Tensor:
+    """pk (the first 32-bit word, unsigned) of float64 [n, 3] pair entries."""
+    return pairs.view(torch.int32).view(-1, 6)[:, 0].to(torch.int64) & 0xFFFFFFFF
+
+
+def _set_pair_pk(pairs: torch.Tensor, pk: torch.Tensor) -> None:
+    words = pairs.view(torch.int32).view(-1, 6)
+    words[:, 0] = torch.where(pk >= 1 << 31, pk - (1 << 32), pk).to(torch.int32)
 
 
 def _names(tensors) -> list:

@@ -200,6 +200,8 @@ class DPEngine:
                             "CalculatePrivateContributionBoundsParams")
         _check_data_extractors(data_extractors)
         self._require_device_backend()
+        pipeline_backend.require_one_process(self._backend,
+                                             "calculate_private_contribution_bounds")
         partitions = _as_collection(partitions)
         backend = self._backend
 

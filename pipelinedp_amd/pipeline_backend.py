@@ -203,6 +203,17 @@ class _HostCollectionOps:
         return iter([list(col)])
 
 
+def require_one_process(backend, what: str) -> None:
+    """Raises NotImplementedError for a call that does not support a backend
+    with several ranks: from host state only, so every rank raises alike,
+    before any device work or collective."""
+    if getattr(backend, "world_size", 1) > 1:
+        raise NotImplementedError(
+            f"{what} is not supported on a backend with world_size > 1: it runs in one "
+            f"process (multi-GPU: DPEngine.aggregate, select_partitions and "
+            f"analysis.perform_utility_analysis on raw rows)")
+
+
 class MI355XBackend(_HostCollectionOps, PipelineBackend):
     """Runs DPEngine.aggregate / select_partitions on one MI355X GPU.
 

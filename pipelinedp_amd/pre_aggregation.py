@@ -16,13 +16,14 @@ pairs.  Utility analysis and the dataset histograms both start from it:
 """
 import ctypes
 import dataclasses
-from typing import Any, Optional
+from typing import Any, Optional, Tuple
 
 import numpy as np
 import torch
 
 from pipelinedp_amd import _native
 from pipelinedp_amd import columnar
+from pipelinedp_amd import distributed
 
 PAIR_DTYPE = np.dtype([("pk", "<u4"), ("count", "<u4"), ("sum", "<f8"), ("np", "<u4"),
                        ("ncl", "<u4")])
@@ -39,14 +40,33 @@ class PairSet:
     n_pairs: int
     key_table: Any                  # dense id -> user key (columnar.decode_keys)
     public_mask: Optional[torch.Tensor]  # device bitmap of public partitions
+    # several ranks: the set holds the partitions lo + i * stride (i <
+    # n_partitions) of the P_global dense ids under local ids i; public_mask is
+    # re-based to them.  n_bad: device int64[1], entries the exchange dropped.
+    owned: Optional[Tuple[int, int, int]] = None
+    n_bad: Optional[torch.Tensor] = None
 
 
 def device_pairs(col, extractors, backend, public_partitions, dev) -> PairSet:
-    """Raw rows -> the pre-aggregate, through dpg_preaggregate."""
+    """Raw rows -> the pre-aggregate, through dpg_preaggregate.
+
+    Several ranks (backend.world_size > 1): the records are placed as
+    ColumnarData(sharding=...) says (distributed.place_records: a privacy id's
+    pairs carry its totals, so it must live on one rank), each rank
+    pre-aggregates its shard and distributed.exchange_owner_pairs moves every
+    pair to its partition's owner: the result is the pre-aggregate of this
+    rank's owned slice of the whole dataset."""
     enc = columnar.encode(col, extractors, dev,
                           need_values=extractors.value_extractor is not None,
                           public_partitions=public_partitions)
     P = enc.n_partitions
+    ranks = backend.world_size
+    if ranks > 1:
+        if not enc.partitions_declared:
+            # every rank must use the same dense partition ids and P
+            raise ValueError(distributed.DENSE_IDS_ERROR)
+        distributed.place_records(
+            enc, backend, col.sharding if isinstance(col, columnar.ColumnarData) else "trusted")
     bound = _native.BoundParams()
     bound.n_partitions = P
     bound.pid_min, bound.pid_count = enc.pid_min, enc.pid_count
@@ -63,6 +83,15 @@ def device_pairs(col, extractors, backend, public_partitions, dev) -> PairSet:
             ctypes.c_void_p(enc.value.data_ptr()) if enc.value is not None else None,
             enc.n, bound, ctypes.c_void_p(pairs.data_ptr()), cap,
             ctypes.c_void_p(starts.data_ptr()), sptr)
+        if ranks > 1:
+            group = backend.process_group
+            own = distributed.owned(P, ranks, torch.distributed.get_rank(group))
+            del starts
+            pairs, starts, n_local, n_pairs, n_bad = distributed.exchange_owner_pairs(
+                pairs, n_pairs, P, group, backend.ctx, sptr)
+            mask = (distributed.slice_bitmap(enc.public_mask, *own)
+                    if enc.public_mask is not None else None)
+            return PairSet(pairs, starts, n_local, n_pairs, enc.key_table, mask, own, n_bad)
     return PairSet(pairs, starts, P, n_pairs, enc.key_table, enc.public_mask)
 
 
