@@ -377,6 +377,51 @@ int dpg_dataset_histograms(dpg_ctx *ctx, const dpg_pair_entry *pairs, int64_t n_
                            const int64_t *partition_start, int64_t n_partitions,
                            int32_t pre_aggregated, const dpg_hist_out *out, void *stream);
 
+/* The same histograms (pre_aggregated = 0) in three phases, for several
+ * ranks: between the phases the caller merges what is not a sum of per-rank
+ * bins -- the per-partition totals (COUNT_PER_PARTITION and
+ * PRIVACY_ID_PER_PARTITION bin a partition by its totals over all ranks) and
+ * the range of the pair sums (the LINF_SUM edges).  L0, L1 and LINF bins of
+ * ranks that hold disjoint privacy ids simply add (counts, sums) and max
+ * (maxima).  All three calls are stream-ordered without a host
+ * synchronisation, record their stages for dpg_last_stage_times ("hist.pairs",
+ * "hist.partials", "hist.partitions", "hist.sums") and return
+ * DPG_ERR_INVALID_ARG for null, negative or oversized arguments.  In one
+ * process dpg_hist_pairs, dpg_hist_partitions on its part_rows / part_count
+ * and dpg_hist_sums on its sum_range give dpg_dataset_histograms' outputs
+ * (integers, edges and maxima bit for bit) and read the pairs as often: twice.
+ *
+ * dpg_hist_pairs: one pass over the pk-sorted pairs of dpg_preaggregate.
+ * Zero-fills int_bins (device [5][DPG_HIST_INT_BINS][3]) and fills histograms
+ * L0, L1 and LINF; writes part_rows[k] (pairs of partition k) and
+ * part_count[k] (records), device int64[n_partitions] -- the rows / count
+ * layout dpg_pack_partials reads -- and sum_range (device double[2]): the
+ * smallest and largest pair sum, (+inf, -inf) when n_pairs == 0 (then pairs
+ * and partition_start may be NULL). */
+int dpg_hist_pairs(dpg_ctx *ctx, const dpg_pair_entry *pairs, int64_t n_pairs,
+                   const int64_t *partition_start, int64_t n_partitions, uint64_t *int_bins,
+                   int64_t *part_rows, int64_t *part_count, double *sum_range, void *stream);
+
+/* Adds COUNT_PER_PARTITION (count) and PRIVACY_ID_PER_PARTITION (rows) of the
+ * n partitions whose totals are given (device int64[n] each) to int_bins; a
+ * partition with rows == 0 opens no bin.  Accumulates: no zero-fill. */
+int dpg_hist_partitions(dpg_ctx *ctx, const int64_t *rows, const int64_t *count, int64_t n,
+                        uint64_t *int_bins, void *stream);
+
+/* LINF_SUM of this rank's pairs between the edges of sum_range (device
+ * double[2]: the range of the whole dataset).  Zero-fills the four outputs
+ * (as dpg_hist_out describes them); with min <= max writes lowers =
+ * np.linspace(min, max, DPG_HIST_SUM_BINS + 1) -- also when n_pairs == 0, so
+ * that every rank holds the same edges -- and bins the pair sums.  min > max
+ * (no pair anywhere): everything stays zero.  sum_max comes out as doubles,
+ * 0.0 in a bin without pairs: a caller that merges ranks takes the maximum
+ * only over the bins whose sum_count is nonzero (distributed.merge_histograms
+ * sends order-preserving integer keys of them, the smallest key for an empty
+ * bin). */
+int dpg_hist_sums(dpg_ctx *ctx, const dpg_pair_entry *pairs, int64_t n_pairs,
+                  const double *sum_range, uint64_t *sum_count, double *sum_sum, double *sum_max,
+                  double *lowers, void *stream);
+
 /* ---- multi-GPU: an RCCL communicator for the partial merge ----
  * One process per GPU, records sharded by privacy id (bounding is then
  * shard-local).  Rank 0 calls dpg_comm_unique_id; the

@@ -20,6 +20,7 @@ EXPORTED = ("dpg_ctx_create", "dpg_ctx_destroy", "dpg_last_error", "dpg_set_seed
             "dpg_compact_kept_async", "dpg_last_stage_times", "dpg_stream_seed",
             "dpg_preaggregate",
             "dpg_utility_analysis", "dpg_dataset_histograms",
+            "dpg_hist_pairs", "dpg_hist_partitions", "dpg_hist_sums",
             "dpg_comm_unique_id", "dpg_ctx_create_comm", "dpg_reduce_scatter_partials",
             "dpg_pack_partials", "dpg_unpack_partials", "dpg_export_error",
             "dpg_import_error", "dpg_shard_records", "dpg_check_shard",
@@ -208,6 +209,12 @@ def load():
         lib.dpg_dataset_histograms.argtypes = [vp, vp, i64, vp, i64, i32,
                                                ctypes.POINTER(HistOut), vp]
         lib.dpg_dataset_histograms.restype = ctypes.c_int
+        lib.dpg_hist_pairs.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp]
+        lib.dpg_hist_pairs.restype = ctypes.c_int
+        lib.dpg_hist_partitions.argtypes = [vp, vp, vp, i64, vp, vp]
+        lib.dpg_hist_partitions.restype = ctypes.c_int
+        lib.dpg_hist_sums.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp]
+        lib.dpg_hist_sums.restype = ctypes.c_int
         lib.dpg_last_stage_times.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t,
                                              ctypes.POINTER(ctypes.c_double), i32,
                                              ctypes.POINTER(ctypes.c_int32)]
@@ -495,6 +502,29 @@ class Context:
                                              n_partitions, int(bool(pre_aggregated)),
                                              ctypes.byref(out), stream)
         self.check(st, "dpg_dataset_histograms")
+
+    def hist_pairs(self, pairs_ptr, n_pairs, starts_ptr, n_partitions, int_bins_ptr,
+                   part_rows_ptr, part_count_ptr, sum_range_ptr, stream):
+        """Phase 1 of the histograms: L0 / L1 / LINF into int_bins (zero-filled),
+        the pairs and records per partition (device int64[n_partitions] each)
+        and the (min, max) pair sum (device double[2])."""
+        st = self.lib.dpg_hist_pairs(self.handle, pairs_ptr, n_pairs, starts_ptr, n_partitions,
+                                     int_bins_ptr, part_rows_ptr, part_count_ptr, sum_range_ptr,
+                                     stream)
+        self.check(st, "dpg_hist_pairs")
+
+    def hist_partitions(self, rows_ptr, count_ptr, n, int_bins_ptr, stream):
+        """Phase 2: adds the per-partition histograms of n partitions' totals."""
+        st = self.lib.dpg_hist_partitions(self.handle, rows_ptr, count_ptr, n, int_bins_ptr,
+                                          stream)
+        self.check(st, "dpg_hist_partitions")
+
+    def hist_sums(self, pairs_ptr, n_pairs, sum_range_ptr, sum_count_ptr, sum_sum_ptr,
+                  sum_max_ptr, lowers_ptr, stream):
+        """Phase 3: LINF_SUM of these pairs between the edges of the given range."""
+        st = self.lib.dpg_hist_sums(self.handle, pairs_ptr, n_pairs, sum_range_ptr,
+                                    sum_count_ptr, sum_sum_ptr, sum_max_ptr, lowers_ptr, stream)
+        self.check(st, "dpg_hist_sums")
 
     def stage_times(self):
         names = ctypes.create_string_buffer(4096)

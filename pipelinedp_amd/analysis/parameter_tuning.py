@@ -18,6 +18,7 @@ import numpy as np
 
 from pipelinedp_amd import aggregate_params as agg
 from pipelinedp_amd import data_extractors as dex
+from pipelinedp_amd import distributed
 from pipelinedp_amd import pipeline_backend
 from pipelinedp_amd.analysis import data_structures
 from pipelinedp_amd.analysis import metrics
@@ -205,12 +206,18 @@ def tune(col, backend, contribution_histograms: histograms.DatasetHistograms,
     utility analysis results) (:278-348).  For select_partitions tuning
     leave options.aggregate_params.metrics empty."""
     _check_tune_args(options, public_partitions is not None)
-    # per-rank histograms would give every rank its own candidate list, and
-    # the utility analysis' all-reduce a different size on every rank
-    pipeline_backend.require_one_process(backend, "parameter_tuning.tune")
+    if options.pre_aggregated_data:
+        pipeline_backend.require_one_process(backend, "parameter_tuning.tune on pre-aggregated data")
+    pipeline_backend.require_declared_partitions(backend, col, "parameter_tuning.tune")
     metric = options.aggregate_params.metrics[0] if options.aggregate_params.metrics else None
     candidates = _find_candidate_parameters(contribution_histograms, options.parameters_to_tune,
                                             metric, options.number_of_parameter_candidates)
+    if getattr(backend, "world_size", 1) > 1:
+        # rank 0's candidates on every rank (one object collective): ranks that
+        # were handed different histograms would otherwise size the utility
+        # analysis' report all-reduce differently
+        candidates = distributed.broadcast_object(candidates, backend.process_group,
+                                                  backend.device)
     ua_options = data_structures.UtilityAnalysisOptions(
         epsilon=options.epsilon, delta=options.delta, aggregate_params=options.aggregate_params,
         multi_param_configuration=candidates,

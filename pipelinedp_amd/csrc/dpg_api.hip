@@ -81,6 +81,7 @@ static hipError_t set_func_attr(const void *kern, hipFuncAttribute attr, int val
 #include "dpg_utility.h"
 #include "dpg_vsum.h"
 #include "dpg_wave.h"
+#include "dpg_hist_phases.h"
 
 using namespace dpg;
 
@@ -2537,6 +2538,118 @@ int dpg_dataset_histograms(dpg_ctx *ctx, const dpg_pair_entry *pairs, int64_t n_
     LAUNCH_CHECK();
     k_hist_finish<<<(kHsBins + kHistThreads - 1) / kHistThreads, kHistThreads, 0, s>>>(a);
     LAUNCH_CHECK();
+    stage(ctx, s, "hist.end");
+    return DPG_OK;
+}
+
+// The histogram call in three phases (several ranks: the per-partition totals
+// and the LINF_SUM range are merged between them).  All
+// three are stream-ordered: no host synchronisation.
+static int hist_begin(dpg_ctx *ctx, hipStream_t s) {
+    (void)hipSetDevice(ctx->device);
+    ctx->stage_names.clear();
+    ctx->n_events_used = 0;
+    ctx->last_stream = s;
+    return DPG_OK;
+}
+
+int dpg_hist_pairs(dpg_ctx *ctx, const dpg_pair_entry *pairs, int64_t n_pairs,
+                   const int64_t *partition_start, int64_t P, uint64_t *int_bins,
+                   int64_t *part_rows, int64_t *part_count, double *sum_range, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (!int_bins || !part_rows || !part_count || !sum_range || P <= 0 || n_pairs < 0 ||
+        (n_pairs > 0 && (!pairs || !partition_start)))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "null argument");
+    if (P >= 0xFFFFFFFFll) return fail(ctx, DPG_ERR_INVALID_ARG, "n_partitions must be < 2^32-1");
+    hipStream_t s = (hipStream_t)stream;
+    int st = hist_begin(ctx, s);
+    stage(ctx, s, "hist.begin");
+    HistArgs a{};
+    a.ib = reinterpret_cast<unsigned long long *>(int_bins);
+    WS(pcount, unsigned int, "hist.pcount", P);
+    WS(minmax, unsigned long long, "hist.minmax", 2);
+    a.pcount = pcount;
+    a.minmax = minmax;
+    HIP_TRY(hipMemsetAsync(a.ib, 0, sizeof(unsigned long long) * kHiTypes * kHiBins * 3, s));
+    HIP_TRY(hipMemsetAsync(pcount, 0, 4 * (size_t)P, s));
+    const unsigned long long mm0[2] = {~0ull, 0ull};
+    UPLOAD(minmax, mm0, sizeof(mm0));
+    stage(ctx, s, "hist.pairs");
+    if (n_pairs > 0) {
+        const unsigned gp = (unsigned)std::min<int64_t>(
+            (n_pairs + kHistThreads - 1) / kHistThreads, (int64_t)ctx->n_cu * 8);
+        k_hist_pairs<false><<<gp, kHistThreads, 0, s>>>(reinterpret_cast<const ItemPA *>(pairs),
+                                                        n_pairs, a);
+        LAUNCH_CHECK();
+    }
+    stage(ctx, s, "hist.partials");
+    k_hist_totals<<<(unsigned)std::min<int64_t>((P + kHistThreads - 1) / kHistThreads,
+                                                (int64_t)ctx->n_cu * 8),
+                    kHistThreads, 0, s>>>(partition_start, P, n_pairs, a, part_rows, part_count,
+                                          sum_range);
+    LAUNCH_CHECK();
+    stage(ctx, s, "hist.end");
+    return DPG_OK;
+}
+
+int dpg_hist_partitions(dpg_ctx *ctx, const int64_t *rows, const int64_t *count, int64_t n,
+                        uint64_t *int_bins, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (!int_bins || n < 0 || (n > 0 && (!rows || !count)))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "null argument");
+    if (n >= 0xFFFFFFFFll) return fail(ctx, DPG_ERR_INVALID_ARG, "n_partitions must be < 2^32-1");
+    hipStream_t s = (hipStream_t)stream;
+    (void)hist_begin(ctx, s);
+    stage(ctx, s, "hist.partitions");
+    if (n > 0) {
+        HistArgs a{};
+        a.ib = reinterpret_cast<unsigned long long *>(int_bins);
+        k_hist_parts_totals<<<(unsigned)std::min<int64_t>((n + kHistThreads - 1) / kHistThreads,
+                                                          (int64_t)ctx->n_cu * 8),
+                              kHistThreads, 0, s>>>(rows, count, n, a);
+        LAUNCH_CHECK();
+    }
+    stage(ctx, s, "hist.end");
+    return DPG_OK;
+}
+
+int dpg_hist_sums(dpg_ctx *ctx, const dpg_pair_entry *pairs, int64_t n_pairs,
+                  const double *sum_range, uint64_t *sum_count, double *sum_sum, double *sum_max,
+                  double *lowers, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (!sum_range || !sum_count || !sum_sum || !sum_max || !lowers || n_pairs < 0 ||
+        (n_pairs > 0 && !pairs))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "null argument");
+    if (n_pairs >= (1ll << 31)) return fail(ctx, DPG_ERR_INVALID_ARG, "n_pairs must be < 2^31");
+    hipStream_t s = (hipStream_t)stream;
+    (void)hist_begin(ctx, s);
+    int st = DPG_OK;
+    stage(ctx, s, "hist.sums");
+    HistArgs a{};
+    a.scount = reinterpret_cast<unsigned long long *>(sum_count);
+    a.ssum = sum_sum;
+    a.smax = reinterpret_cast<unsigned long long *>(sum_max);
+    a.lowers = lowers;
+    WS(keys, unsigned long long, "hist.range_keys", 2);
+    a.minmax = keys;
+    HIP_TRY(hipMemsetAsync(a.scount, 0, 8 * kHsBins, s));
+    HIP_TRY(hipMemsetAsync(a.ssum, 0, 8 * kHsBins, s));
+    HIP_TRY(hipMemsetAsync(a.smax, 0, 8 * kHsBins, s));
+    k_hist_range_keys<<<1, 1, 0, s>>>(sum_range, a);
+    LAUNCH_CHECK();
+    // the edges on every rank, pairs or none; an empty range gives all zeros
+    k_hist_lowers<<<(kHsBins + kHistThreads) / kHistThreads, kHistThreads, 0, s>>>(a);
+    LAUNCH_CHECK();
+    if (n_pairs > 0) {
+        const size_t lds = (size_t)kHsBins * (4 + 8);
+        (void)set_func_attr((const void *)k_hist_sums, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds);
+        k_hist_sums<<<(unsigned)std::min<int64_t>((n_pairs + 1023) / 1024, (int64_t)ctx->n_cu),
+                      1024, lds, s>>>(reinterpret_cast<const ItemPA *>(pairs), n_pairs, a);
+        LAUNCH_CHECK();
+        k_hist_finish<<<(kHsBins + kHistThreads - 1) / kHistThreads, kHistThreads, 0, s>>>(a);
+        LAUNCH_CHECK();
+    }
     stage(ctx, s, "hist.end");
     return DPG_OK;
 }

@@ -11,6 +11,15 @@ dpg_hist.h: streaming passes over the pairs and the partitions into
 LDS-privatised bins).  The host only turns the few thousand non-empty bins
 into FrequencyBin objects.
 
+Several ranks (backend.world_size > 1, an input that declares its partitions;
+DESIGN.md section 14): the pairs do not travel.  Every rank runs the call's
+three phases on the pre-aggregate of its own privacy ids (dpg_hist_pairs,
+dpg_hist_partitions, dpg_hist_sums) and between them the ranks merge what is
+not a sum of bins -- the range of the pair sums (distributed.hist_header) and
+the per-partition totals (distributed.exchange_partials) -- then the bins
+(distributed.merge_histograms): five collectives, and every rank holds the
+DatasetHistograms of the whole dataset.
+
 compute_dataset_histograms_on_preaggregated_data (:642-684) takes
 PreAggregateExtractors rows instead; L0 / L1 are then weighted by
 1 / n_partitions per exact value and rounded (:81-102, 482-529).
@@ -23,6 +32,7 @@ import torch
 
 from pipelinedp_amd import _native
 from pipelinedp_amd import data_extractors as dex
+from pipelinedp_amd import distributed
 from pipelinedp_amd import pipeline_backend
 from pipelinedp_amd import pre_aggregation
 from pipelinedp_amd.dataset_histograms import histograms as hist
@@ -82,7 +92,10 @@ def _float_histogram(count, sums, maxes, lowers) -> hist.Histogram:
 
 def histograms_from_pairs(ps: pre_aggregation.PairSet, backend,
                           pre_aggregated: bool) -> hist.DatasetHistograms:
-    """dpg_dataset_histograms over a pre-aggregate, bins to the host."""
+    """dpg_dataset_histograms over a pre-aggregate, bins to the host.  On a
+    backend with several ranks ps is the rank's local pre-aggregate
+    (pre_aggregation.device_pairs(exchange=False)) and the result is the
+    whole dataset's, the same on every rank."""
     dev = ps.pairs.device
     nb, ns = _native.HIST_INT_BINS, _native.HIST_SUM_BINS
     u64 = dict(dtype=torch.int64, device=dev)
@@ -95,9 +108,15 @@ def histograms_from_pairs(ps: pre_aggregation.PairSet, backend,
                           lowers.data_ptr())
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        backend.ctx.dataset_histograms(ctypes.c_void_p(ps.pairs.data_ptr()), ps.n_pairs,
-                                       ctypes.c_void_p(ps.starts.data_ptr()), ps.n_partitions,
-                                       pre_aggregated, out, ctypes.c_void_p(stream.cuda_stream))
+        if backend.world_size > 1:
+            assert not pre_aggregated and ps.owned is None
+            ib, sc, ss, sm = _phases_over_ranks(ps, backend, ib, sc, ss, sm, lowers,
+                                                ctypes.c_void_p(stream.cuda_stream))
+        else:
+            backend.ctx.dataset_histograms(ctypes.c_void_p(ps.pairs.data_ptr()), ps.n_pairs,
+                                           ctypes.c_void_p(ps.starts.data_ptr()),
+                                           ps.n_partitions, pre_aggregated, out,
+                                           ctypes.c_void_p(stream.cuda_stream))
         stream.synchronize()
     ib_h = ib.cpu().numpy().view(np.uint64)
     hs = {t: _int_histogram(t, ib_h[i]) for i, t in enumerate(_INT_TYPES)}
@@ -108,6 +127,33 @@ def histograms_from_pairs(ps: pre_aggregation.PairSet, backend,
                                   hs[T.LINF_CONTRIBUTIONS], lin_sum,
                                   hs[T.COUNT_PER_PARTITION],
                                   hs[T.COUNT_PRIVACY_ID_PER_PARTITION])
+
+
+def _phases_over_ranks(ps, backend, ib, sc, ss, sm, lowers, sptr):
+    """The three phases on this rank's pairs with the merges between them;
+    returns the whole dataset's (int_bins, sum_count, sum_sum, sum_max);
+    `lowers` holds the whole dataset's edges on every rank.  Collectives, run
+    by every rank whatever it holds: the header (max), the totals' exchange,
+    and the bin merge's three."""
+    ctx, group = backend.ctx, backend.process_group
+    dev, P = ps.pairs.device, ps.n_partitions
+    rows = torch.empty(P, dtype=torch.int64, device=dev)
+    count = torch.empty(P, dtype=torch.int64, device=dev)
+    local_range = torch.empty(2, dtype=torch.float64, device=dev)
+    ctx.hist_pairs(ps.pairs.data_ptr(), ps.n_pairs, ps.starts.data_ptr(), P, ib.data_ptr(),
+                   rows.data_ptr(), count.data_ptr(), local_range.data_ptr(), sptr)
+    # the route's one host synchronisation: the occupancy bound of the exchange
+    sum_range, bound = distributed.hist_header(local_range, min(P, ps.n_pairs), group)
+    totals, (_, _, n_own), _, flags = distributed.exchange_partials(
+        {"rows": rows, "count": count}, P, group, mode=backend.exchange, nnz_bound=bound,
+        ctx=ctx, stream=sptr)
+    own_rows, own_count = totals["rows"].contiguous(), totals["count"].contiguous()
+    ctx.hist_partitions(own_rows.data_ptr() if n_own else None,
+                        own_count.data_ptr() if n_own else None, n_own, ib.data_ptr(), sptr)
+    sum_range = sum_range.contiguous()
+    ctx.hist_sums(ps.pairs.data_ptr(), ps.n_pairs, sum_range.data_ptr(), sc.data_ptr(),
+                  ss.data_ptr(), sm.data_ptr(), lowers.data_ptr(), sptr)
+    return distributed.merge_histograms(ib, sc, ss, sm, flags, group)
 
 
 class _OneElement:
@@ -133,12 +179,17 @@ def _require_device_backend(backend):
 
 def compute_dataset_histograms(col, data_extractors: dex.DataExtractors, backend):
     """1-element collection with the DatasetHistograms of the rows
-    (computing_histograms.py:420-474)."""
+    (computing_histograms.py:420-474).  On a backend with several ranks col
+    must be ColumnarData(n_partitions=P) (its `sharding` means what it means
+    for aggregate; anything else raises NotImplementedError here, from host
+    state only), every rank has to iterate the result, and every rank gets
+    the histograms of the whole dataset."""
     _require_device_backend(backend)
-    pipeline_backend.require_one_process(backend, "compute_dataset_histograms")
+    pipeline_backend.require_declared_partitions(backend, col, "compute_dataset_histograms")
 
     def run():
-        ps = pre_aggregation.device_pairs(col, data_extractors, backend, None, backend.device)
+        ps = pre_aggregation.device_pairs(col, data_extractors, backend, None, backend.device,
+                                          exchange=False)
         return histograms_from_pairs(ps, backend, pre_aggregated=False)
 
     return _OneElement(run)

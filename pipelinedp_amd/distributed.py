@@ -46,6 +46,12 @@ R sorted runs it receives into the owned slice's pre-aggregate
 ranks -- the selection probability is a convolution over a partition's pairs
 -- so the pairs, not partials, have to meet.
 
+The dataset histograms move neither records nor pairs: their bins are sums
+over ranks once the per-partition totals (`exchange_partials` of rows and
+count) and the range of the pair sums (`hist_header`) are global;
+`merge_histograms` then adds and maxes the bins in three all_reduces
+(DESIGN.md section 14).
+
 Ownership is by partition key: rank r owns partitions r, r + R, r + 2R, ...
 (R ranks; `pk mod R`, the identity hash of the dense ids), at local index
 pk // R.  Interleaving spreads hot low ids -- an unpermuted Zipf key space
@@ -659,6 +665,94 @@ def exchange_partials(tensors: Dict[str, Optional[torch.Tensor]], P: int, group,
             "nnz_bound": bound,
             "send_bytes": exchange_bytes(P, bound, len(names), world)[chosen]}
     return out, own, info, flags
+
+
+def _all_reduce(t: torch.Tensor, op, group) -> torch.Tensor:
+    """all_reduce of t on its device under nccl, staged through the host
+    under gloo; the result on t's device."""
+    if _is_nccl(group) or t.device.type == "cpu":
+        dist.all_reduce(t, op=op, group=group)
+        return t
+    host = t.cpu()
+    dist.all_reduce(host, op=op, group=group)
+    return host.to(t.device)
+
+
+def hist_header(sum_range: torch.Tensor, n_bound: int, group):
+    """ONE all_reduce (max) before the dataset histograms' exchange, of
+    [-min, max, n_bound] as float64: the range of the pair sums over all ranks
+    (negating the min is exact; a rank without pairs holds (+inf, -inf) and
+    changes nothing) and the largest per-rank occupancy bound, which every
+    rank then passes to `choose_exchange`.  sum_range: float64[2] (min, max).
+    Returns (range, bound): the float64[2] range of the whole dataset on
+    sum_range's device -- (+inf, -inf) if no rank has a pair -- and the bound
+    as an int; reading it synchronises the host."""
+    t = torch.stack([-sum_range[0], sum_range[1],
+                     torch.tensor(float(n_bound), dtype=torch.float64,
+                                  device=sum_range.device)])
+    t = _all_reduce(t, dist.ReduceOp.MAX, group)
+    return torch.stack([-t[0], t[1]]), int(t[2].item())
+
+
+_KEY_FLIP = (1 << 63) - 1
+
+
+def _ordered_keys(b: torch.Tensor) -> torch.Tensor:
+    """The bit patterns (int64) of float64 values -> int64 keys whose signed
+    order is the values' order, and back: the map is its own inverse."""
+    return torch.where(b >= 0, b, b ^ _KEY_FLIP)
+
+
+def merge_histograms(int_bins: torch.Tensor, sum_count: torch.Tensor, sum_sum: torch.Tensor,
+                     sum_max: torch.Tensor, flags: Optional[torch.Tensor], group):
+    """Merges every rank's histogram bins into the bins of the whole dataset,
+    the same on every rank, with THREE collectives:
+
+    * one int64 SUM: the counts and sums of the integer bins
+      (int_bins[..., 0:2]; int64 [T, bins, 3]: count, sum, max), the LINF_SUM
+      counts and one slot of error flags (`flags`: any tensor, e.g. the
+      exchange's, nonzero = this rank saw an error);
+    * one int64 MAX: the integer maxima (int_bins[..., 2]) and the LINF_SUM
+      maxima as order-preserving integer keys, INT64_MIN where this rank's
+      bin is empty (a float maximum of 0.0 there would beat negative sums);
+    * one float64 SUM: the LINF_SUM sums.
+
+    Every rank runs all three whatever it holds.  A nonzero flag total raises
+    RuntimeError on every rank, after the collectives.  Returns (int_bins,
+    sum_count, sum_sum, sum_max) on the inputs' device; sum_max is 0.0 in a
+    bin that is empty on every rank."""
+    T, nb, _ = int_bins.shape
+    ns = sum_count.numel()
+    dev = int_bins.device
+    bad = (torch.zeros(1, dtype=torch.int64, device=dev) if flags is None
+           else (flags.to(dev) != 0).sum().reshape(1).to(torch.int64))
+    adds = torch.cat([int_bins[:, :, 0:2].reshape(-1), sum_count.reshape(-1), bad])
+    keys = torch.where(sum_count > 0, _ordered_keys(sum_max.contiguous().view(torch.int64)),
+                       torch.full_like(sum_count, _I64_MIN))
+    maxes = torch.cat([int_bins[:, :, 2].reshape(-1), keys])
+    adds = _all_reduce(adds, dist.ReduceOp.SUM, group)
+    maxes = _all_reduce(maxes, dist.ReduceOp.MAX, group)
+    sums = _all_reduce(sum_sum.clone(), dist.ReduceOp.SUM, group)
+    n_bad = int(adds[-1].item())
+    if n_bad:
+        raise RuntimeError(f"dataset histograms: {n_bad} ranks reported an error in the "
+                           f"exchange of the per-partition totals")
+    merged = torch.empty_like(int_bins)
+    merged[:, :, 0:2] = adds[:T * nb * 2].view(T, nb, 2)
+    merged[:, :, 2] = maxes[:T * nb].view(T, nb)
+    count = adds[T * nb * 2:T * nb * 2 + ns].contiguous()
+    k = maxes[T * nb:]
+    top = torch.where(count > 0, _ordered_keys(k), torch.zeros_like(k)).view(torch.float64)
+    return merged, count, sums, top
+
+
+def broadcast_object(obj, group, device):
+    """Rank 0's (small, picklable) object on every rank: one object collective."""
+    root = dist.get_global_rank(group, 0) if group is not None else 0
+    box = [obj if dist.get_rank() == root else None]
+    dist.broadcast_object_list(box, src=root, group=group,
+                               device=device if _is_nccl(group) else None)
+    return box[0]
 
 
 def slice_bitmap(mask: torch.Tensor, lo: int, stride: int, n: int) -> torch.Tensor:

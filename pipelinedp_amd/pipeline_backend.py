@@ -210,8 +210,30 @@ def require_one_process(backend, what: str) -> None:
     if getattr(backend, "world_size", 1) > 1:
         raise NotImplementedError(
             f"{what} is not supported on a backend with world_size > 1: it runs in one "
-            f"process (multi-GPU: DPEngine.aggregate, select_partitions and "
-            f"analysis.perform_utility_analysis on raw rows)")
+            f"process (multi-GPU: DPEngine.aggregate, select_partitions, "
+            f"analysis.perform_utility_analysis on raw rows and, over "
+            f"ColumnarData(n_partitions=P), the dataset histograms, private contribution "
+            f"bounds and tune)")
+
+
+def require_declared_partitions(backend, col, what: str) -> None:
+    """The dataset histograms and what is built on them (private contribution
+    bounds, tune) run on several ranks only over an input that declares its
+    dense partition ids -- ColumnarData(n_partitions=P), or a mapping with
+    'n_partitions' (columnar.encode's hint) -- since every rank must bin the
+    same P partitions.  Anything else raises NotImplementedError: from host
+    state only, as require_one_process."""
+    if getattr(backend, "world_size", 1) <= 1:
+        return
+    if isinstance(col, columnar.ColumnarData):
+        hint = col.n_partitions
+    else:
+        hint = col.get("n_partitions") if isinstance(col, typing.Mapping) else None
+    if hint is None:
+        raise NotImplementedError(
+            f"{what} on a backend with world_size > 1 needs an input that declares its "
+            f"partitions: pass ColumnarData(..., n_partitions=P) with dense ids pk in [0, P) on "
+            f"every rank (rows and undeclared columns run in one process)")
 
 
 class MI355XBackend(_HostCollectionOps, PipelineBackend):

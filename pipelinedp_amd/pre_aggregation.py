@@ -47,7 +47,8 @@ class PairSet:
     n_bad: Optional[torch.Tensor] = None
 
 
-def device_pairs(col, extractors, backend, public_partitions, dev) -> PairSet:
+def device_pairs(col, extractors, backend, public_partitions, dev,
+                 exchange: bool = True) -> PairSet:
     """Raw rows -> the pre-aggregate, through dpg_preaggregate.
 
     Several ranks (backend.world_size > 1): the records are placed as
@@ -55,7 +56,10 @@ def device_pairs(col, extractors, backend, public_partitions, dev) -> PairSet:
     pairs carry its totals, so it must live on one rank), each rank
     pre-aggregates its shard and distributed.exchange_owner_pairs moves every
     pair to its partition's owner: the result is the pre-aggregate of this
-    rank's owned slice of the whole dataset."""
+    rank's owned slice of the whole dataset.  exchange=False (the dataset
+    histograms, whose bins are sums over ranks) stops before that exchange:
+    the result is the pre-aggregate of this rank's privacy ids under the
+    global partition ids and the global P."""
     enc = columnar.encode(col, extractors, dev,
                           need_values=extractors.value_extractor is not None,
                           public_partitions=public_partitions)
@@ -83,7 +87,7 @@ def device_pairs(col, extractors, backend, public_partitions, dev) -> PairSet:
             ctypes.c_void_p(enc.value.data_ptr()) if enc.value is not None else None,
             enc.n, bound, ctypes.c_void_p(pairs.data_ptr()), cap,
             ctypes.c_void_p(starts.data_ptr()), sptr)
-        if ranks > 1:
+        if ranks > 1 and exchange:
             group = backend.process_group
             own = distributed.owned(P, ranks, torch.distributed.get_rank(group))
             del starts
