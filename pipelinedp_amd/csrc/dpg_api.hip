@@ -1372,6 +1372,8 @@ int run_level1_pieces(dpg_ctx *ctx, hipStream_t s, const SrcSoAKey<R, true> &src
                       uint32_t F, uint32_t bits, uint32_t C, R *out, Control *ctl,
                       PieceTab *pt, uint32_t *host_tot) {
     int st = DPG_OK;
+    // (k_scatter's kEarly: a one-record last tile loads the record before it too)
+    if (n < 2) return fail(ctx, DPG_ERR_HIP, "internal: piece level needs two records");
     const int64_t sub = (int64_t)NT * IPT;
     const uint32_t nt = (uint32_t)((n + sub - 1) / sub);
     WS(tiles, TileDesc, "pieces.tiles", nt);

@@ -804,10 +804,17 @@ struct PcRsv {
     unsigned long long old[DPT / 2];
 };
 // NT threads, DPT (even) consecutive digits per thread: DPT / 2 64-bit
-// reservations per thread
-template <int NT, int DPT>
+// reservations per thread.  between(): run after the reservations are
+// issued and before the first barrier (k_scatter's DPG_L1_PF 3 issues the
+// next sub-tile's loads there: younger than the reservations in the vmcnt
+// order, so scatter_rsv_finish waits for the atomics and not for the loads).
+struct NoBetween {
+    __device__ __forceinline__ void operator()() const {}
+};
+template <int NT, int DPT, class Between = NoBetween>
 __device__ __forceinline__ uint32_t scatter_scan_pc(uint32_t *cnt, uint32_t *dstart, uint32_t F,
-                                                    uint32_t *sh16, uint32_t *goff, PcRsv<DPT> &r) {
+                                                    uint32_t *sh16, uint32_t *goff, PcRsv<DPT> &r,
+                                                    Between between = Between{}) {
     const uint32_t d0 = DPT * threadIdx.x;
     uint32_t x = 0;
 #pragma unroll
@@ -824,6 +831,7 @@ __device__ __forceinline__ uint32_t scatter_scan_pc(uint32_t *cnt, uint32_t *dst
     for (int q = 0; q < DPT / 2; ++q)
         r.old[q] = atomicAdd(reinterpret_cast<unsigned long long *>(&goff[(d0 + 2 * q) % F]),
                              (unsigned long long)r.c[2 * q] | ((unsigned long long)r.c[2 * q + 1] << 32));
+    between();
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     uint32_t wt;
     uint32_t e = wave_excl_scan(x, wt);
@@ -973,6 +981,28 @@ constexpr size_t scatter_lds_core() {
 #ifndef DPG_PC_LATE_RSV
 #define DPG_PC_LATE_RSV 1
 #endif
+// Piece mode (SrcSoAKey<R, true>: decode packs rec[] from raw[], so raw[] is
+// dead once a sub-tile is ranked): where k_scatter issues the next
+// sub-tile's loads.
+//   0  after the staging barrier, before the write-out, as every other
+//      source does; the pair loads' clamp then selects inside the load
+//      block, where the compiler waits for it -- s_waitcnt vmcnt(7) ..
+//      vmcnt(0) right behind the eight loads (tools/loopmap.py), so none of
+//      them is in flight during the write-out
+//   2  between the digit scan and the staging
+//   3  inside the digit scan, after the run reservations and before its
+//      first barrier (scatter_scan_pc's between)
+// With 2 and 3 the loads are in flight during the staging (__syncthreads
+// waits for lgkmcnt only) and the write-out, and the load block holds no
+// select and no branch, either of which the compiler guards with a wait
+// for everything in flight: raw[] keeps the loaded pairs and the next
+// sub-tile's decode makes the clamp's choice; a one-record sub-tile loads the
+// pair that starts one record before it; a workgroup's last sub-tile loads
+// itself again.  scatter_rsv_finish then waits for the reservations with
+// vmcnt(<loads issued>).
+#ifndef DPG_L1_PF
+#define DPG_L1_PF 2
+#endif
 template <class Src, class Rec, int IPT, int FMAX, int NT = kScatThreads>
 constexpr bool scatter_lbase() {
     return scatter_lds_core<Src, Rec, IPT, FMAX, NT>() + (size_t)FMAX * 4 <= 160 * 1024;
@@ -989,6 +1019,7 @@ constexpr size_t scatter_lds() {
 // ranked (load waits + decode + LDS ranking + barrier), [1] digit scan
 // and run reservations, [2] staging + barrier,
 // [3] next loads issued + write-out, [4] tile transitions, [5] sub-tiles.
+// (Piece mode with DPG_L1_PF 2 / 3: the next loads are issued in [1].)
 #ifdef DPG_PHASE_TIMING
 __device__ unsigned long long g_scat_cyc[8];
 #define DPG_SCAT_MARK(k)                                         \
@@ -1038,6 +1069,9 @@ __global__ __launch_bounds__(NT, 4) void k_scatter(Src src_in, const TileDesc *t
     constexpr bool kPc = HasPieces<Src>::value;
     constexpr bool kSD = !Src::kDigitFromRec;
     constexpr bool kP = HasFetchPairs<Src>::value && IPT % 2 == 0;
+    // piece mode: the next sub-tile's loads before the staging (DPG_L1_PF)
+    constexpr bool kEarly = kPc && kP && DPG_L1_PF != 0;
+    constexpr int kPF = kEarly ? DPG_L1_PF : 0;
     using W = Words<Rec>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     W *stage = reinterpret_cast<W *>(smem);  // [SUB + 1]: slot SUB takes dropped records
@@ -1072,8 +1106,9 @@ __global__ __launch_bounds__(NT, 4) void k_scatter(Src src_in, const TileDesc *t
     // software pipeline: the raw loads of the next sub-tile -- of this tile,
     // or the first one of the next tile -- are issued right after the
     // current sub-tile is staged in LDS, so they are in flight during its
-    // write-out.  (Grouped XCD-local levels have one sub-tile per tile: the
-    // next tile's id is dequeued at the start of the current one.)
+    // write-out (piece mode, kEarly: before the staging, see DPG_L1_PF).
+    // (Grouped XCD-local levels have one sub-tile per tile: the next tile's
+    // id is dequeued at the start of the current one.)
     // Loads are unconditional with the index clamped into the sub-tile (a
     // guarded load becomes a branch with its own vmcnt(0) wait, serialising
     // the sub-tile's loads); lanes past the end re-read the last record.
@@ -1086,7 +1121,18 @@ __global__ __launch_bounds__(NT, 4) void k_scatter(Src src_in, const TileDesc *t
     // loads singly)
     typename Src::Raw raw[IPT];
     auto load_sub = [&](int64_t b0, uint32_t lim) {
-        if constexpr (kP) {
+        if constexpr (kEarly) {
+            // the pairs as loaded, for any lim >= 1: lim == 1 loads the
+            // pair that starts one record before the sub-tile (piece mode's
+            // only one-record sub-tile is the last tile of an input of
+            // n >= 2 records, run_level1_pieces: that record exists)
+#pragma unroll
+            for (int m = 0; m < IPT / 2; ++m) {
+                const int32_t o = m * 2 * NT + 2 * tid;
+                src.fetch2(b0 + min(o, (int32_t)lim - 2), raw[2 * m], raw[2 * m + 1]);
+            }
+            return;
+        } else if constexpr (kP) {
             if (lim >= 2) {
 #pragma unroll
                 for (int m = 0; m < IPT / 2; ++m) {
@@ -1102,6 +1148,16 @@ __global__ __launch_bounds__(NT, 4) void k_scatter(Src src_in, const TileDesc *t
         }
 #pragma unroll
         for (int j = 0; j < IPT; ++j) raw[j] = src.fetch(b0 + min(elem(j), lim - 1));
+    };
+    // kEarly: decodes element j of a sub-tile of lim records; the clamp's
+    // choice between the two loaded records is made here (an even element
+    // past lim - 2 is the pair's second record)
+    auto decode_raw = [&](int j, uint32_t lim, int64_t i, Rec &r, uint32_t &d) -> bool {
+        if constexpr (kEarly) {
+            if ((j & 1) == 0)
+                return src.decode((int32_t)elem(j) > (int32_t)lim - 2 ? raw[j + 1] : raw[j], i, r, d);
+        }
+        return src.decode(raw[j], i, r, d);
     };
     // the first tile (tiles are never empty: the tile builders cut
     // ceil(n / tile) tiles of n > 0 records)
@@ -1191,7 +1247,10 @@ __global__ __launch_bounds__(NT, 4) void k_scatter(Src src_in, const TileDesc *t
             for (int j = 0; j < IPT; ++j) {
                 const uint32_t o = elem(j);
                 uint32_t d = 0;
-                okv[j] = o < lim && src.decode(raw[j], sb + o, rec[j], d);
+                if constexpr (kEarly)
+                    okv[j] = o < lim && decode_raw(j, lim, sb + o, rec[j], d);
+                else
+                    okv[j] = o < lim && src.decode(raw[j], sb + o, rec[j], d);
                 dg[j] = okv[j] ? d : 0u;
             }
             uint32_t rk[IPT];
@@ -1206,7 +1265,11 @@ __global__ __launch_bounds__(NT, 4) void k_scatter(Src src_in, const TileDesc *t
             for (int j = 0; j < IPT; ++j) {
                 const uint32_t o = elem(j);
                 uint32_t d = 0;
-                const bool ok = o < lim && src.decode(raw[j], sb + o, rec[j], d);
+                bool ok;
+                if constexpr (kEarly)
+                    ok = o < lim && decode_raw(j, lim, sb + o, rec[j], d);
+                else
+                    ok = o < lim && src.decode(raw[j], sb + o, rec[j], d);
                 const uint32_t rk = wave_agg_rank(cnt, ok ? d : 0u, ok, bits);
                 dr[j] = ok ? (d | (rk << 12)) : ~0u;
             }
@@ -1218,6 +1281,7 @@ __global__ __launch_bounds__(NT, 4) void k_scatter(Src src_in, const TileDesc *t
         constexpr bool kLate = kPcLB && (kDPT == 2 || kDPT == 4) && FMAX == kDPT * NT && DPG_PC_LATE_RSV;
         PcRsv<(kDPT >= 2 ? kDPT : 2)> rsv;
         uint32_t total;
+        if constexpr (!kEarly) {
         if constexpr (kLate)
             total = scatter_scan_pc<NT, kDPT>(cnt, dstart, F, sh16, gof, rsv);
         else
@@ -1268,6 +1332,56 @@ __global__ __launch_bounds__(NT, 4) void k_scatter(Src src_in, const TileDesc *t
                 }
             }
             if (ll > 0) load_sub(lb, ll);
+        }
+        } else {
+        // piece mode, DPG_L1_PF: raw[] is dead once the sub-tile is ranked,
+        // so the next loads -- the next sub-tile of this tile or the first of
+        // the workgroup's next tile (bounds computed, as above) -- are issued
+        // before the staging.  No branch around them: a workgroup's last
+        // sub-tile loads itself again (never decoded)
+        auto prefetch = [&]() {
+            const int64_t nb = sb + SUB;
+            const uint32_t nlim = (uint32_t)max<int64_t>(0, min<int64_t>(SUB, td.end - nb));
+            int64_t lb = nb;
+            uint32_t ll = nlim;
+            if (nlim == 0) {
+                lb = sb;
+                ll = lim;
+                if (it + gridDim.x < nt) {
+                    tn = it + gridDim.x;
+                    tdn.begin = (int64_t)tn * SUB;
+                    tdn.end = min(tdn.begin + SUB, n_end);
+                    lb = tdn.begin;
+                    ll = (uint32_t)min<int64_t>(SUB, tdn.end - tdn.begin);
+                }
+            }
+            load_sub(lb, ll);
+        };
+        if constexpr (kLate && kPF == 3) {
+            total = scatter_scan_pc<NT, kDPT>(cnt, dstart, F, sh16, gof, rsv, prefetch);
+        } else {
+            if constexpr (kLate)
+                total = scatter_scan_pc<NT, kDPT>(cnt, dstart, F, sh16, gof, rsv);
+            else
+                total = scatter_scan_update<NT, FMAX / NT, kPc>(
+                    cnt, dstart, cur, F, sh16, gof, pcap, pdump, perr, kPcLB ? lbase : nullptr);
+            prefetch();
+        }
+        DPG_SCAT_MARK(1);
+        {
+            uint32_t ds[IPT];
+#pragma unroll
+            for (int j = 0; j < IPT; ++j) ds[j] = dstart[dr[j] != ~0u ? (dr[j] & 0xFFFu) : 0u];
+#pragma unroll
+            for (int j = 0; j < IPT; ++j) {
+                const uint32_t pos = dr[j] != ~0u ? ds[j] + (dr[j] >> 12) : (uint32_t)SUB;
+                stage[pos] = to_words(rec[j]);
+                if constexpr (kSD) sdig[pos] = (uint16_t)(dr[j] & 0xFFFu);
+            }
+        }
+        if constexpr (kLate) scatter_rsv_finish(rsv, cur, lbase, F, pcap, pdump, perr);
+        __syncthreads();
+        DPG_SCAT_MARK(2);
         }
         // write-out in batches of WB staged records per thread, branch-free:
         // slots past the end repeat the last staged record, whose store they
