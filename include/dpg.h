@@ -422,6 +422,37 @@ int dpg_hist_sums(dpg_ctx *ctx, const dpg_pair_entry *pairs, int64_t n_pairs,
                   const double *sum_range, uint64_t *sum_count, double *sum_sum, double *sum_max,
                   double *lowers, void *stream);
 
+/* The utility analysis' partition sampler (partitions_sampling_prob < 1,
+ * pipeline_dp/sampling_utils.py:32-51) for integer partition keys.  Key i is
+ * keys[i] (device int64[n]) or, with keys == NULL, key_lo + i * key_stride
+ * (dense ids; several ranks: the owned slice).  H(key) is the big-endian
+ * first 8 bytes of SHA-1 over the ASCII decimal repr of the signed key ("-"
+ * for negatives, no leading zeros), i.e.
+ * int(hashlib.sha1(repr(key).encode()).hexdigest()[:16], 16).  Bit i of mask
+ * (bit i & 7 of byte i >> 3, the layout dpg_ua_params.sample_mask reads) is
+ * set iff keep_all != 0 or H(key_i) < bound, compared as unsigned 64-bit
+ * integers; keep_all stands for the bound 2^64 (round(2^64 * p) for p just
+ * below 1).  mask: device, 8 * ceil(n / 64) bytes, 8-byte aligned; every bit
+ * at an index >= n inside it is written as 0.  hashes (device uint64[n], or
+ * NULL) receives H of every key.  Stream-ordered, no host synchronisation;
+ * the stage is appended to the running list of dpg_last_stage_times as
+ * "ua.sample" (closed by the mark "ua.sampled"; a call right behind another
+ * replaces its entry).  A null mask, n < 0 or a misaligned pointer:
+ * DPG_ERR_INVALID_ARG. */
+int dpg_sample_partitions(dpg_ctx *ctx, const int64_t *keys, int64_t key_lo, int64_t key_stride,
+                          int64_t n, uint64_t bound, int32_t keep_all, uint8_t *mask,
+                          uint64_t *hashes, void *stream);
+
+/* How a public-partition list relates to the data
+ * (analysis/dataset_summary.py): pk (device int64[n]) holds dense ids in
+ * [0, n_partitions), public_mask is the device bitmap of the public ones.
+ * counts (device int64[3]) receives the number of partitions that are
+ * present in pk and public, present and not public, public and not present.
+ * Synchronises the stream once; a key outside [0, n_partitions):
+ * DPG_ERR_KEY_RANGE. */
+int dpg_partition_summary(dpg_ctx *ctx, const int64_t *pk, int64_t n, int64_t n_partitions,
+                          const uint8_t *public_mask, int64_t *counts, void *stream);
+
 /* ---- multi-GPU: an RCCL communicator for the partial merge ----
  * One process per GPU, records sharded by privacy id (bounding is then
  * shard-local).  Rank 0 calls dpg_comm_unique_id; the

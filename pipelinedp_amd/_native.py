@@ -26,7 +26,8 @@ EXPORTED = ("dpg_ctx_create", "dpg_ctx_destroy", "dpg_last_error", "dpg_set_seed
             "dpg_import_error", "dpg_shard_records", "dpg_check_shard",
             "dpg_owner_split_keys", "dpg_owner_split_pairs", "dpg_merge_pair_runs",
             "dpg_sort_pairs_u64", "dpg_bound_records", "dpg_quantile_keys", "dpg_quantiles",
-            "dpg_vector_index", "dpg_vector_sums", "dpg_vector_clip_noise")
+            "dpg_vector_index", "dpg_vector_sums", "dpg_vector_clip_noise",
+            "dpg_sample_partitions", "dpg_partition_summary")
 
 COMM_ID_BYTES = 128  # DPG_COMM_ID_BYTES
 
@@ -266,6 +267,11 @@ def load():
         lib.dpg_vector_clip_noise.argtypes = [vp, vp, i64, ctypes.POINTER(VectorParams), vp, vp,
                                               vp]
         lib.dpg_vector_clip_noise.restype = ctypes.c_int
+        lib.dpg_sample_partitions.argtypes = [vp, vp, i64, i64, i64, ctypes.c_uint64, i32, vp, vp,
+                                              vp]
+        lib.dpg_sample_partitions.restype = ctypes.c_int
+        lib.dpg_partition_summary.argtypes = [vp, vp, i64, i64, vp, vp, vp]
+        lib.dpg_partition_summary.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -525,6 +531,24 @@ class Context:
         st = self.lib.dpg_hist_sums(self.handle, pairs_ptr, n_pairs, sum_range_ptr,
                                     sum_count_ptr, sum_sum_ptr, sum_max_ptr, lowers_ptr, stream)
         self.check(st, "dpg_hist_sums")
+
+    def sample_partitions(self, keys_ptr, key_lo, key_stride, n, bound: int, mask_ptr,
+                          hashes_ptr, stream):
+        """Device bitmap at mask_ptr (8 * ceil(n / 64) bytes) of the keys whose
+        sampler hash is below bound (an int in [0, 2^64]; 2^64 keeps all);
+        keys_ptr None: the keys key_lo + i * key_stride.  Stream-ordered."""
+        keep_all = bound >= 2**64
+        st = self.lib.dpg_sample_partitions(self.handle, keys_ptr, int(key_lo), int(key_stride),
+                                            int(n), ctypes.c_uint64(0 if keep_all else bound),
+                                            int(keep_all), mask_ptr, hashes_ptr, stream)
+        self.check(st, "dpg_sample_partitions")
+
+    def partition_summary(self, pk_ptr, n, n_partitions, public_mask_ptr, counts_ptr, stream):
+        """Device int64[3] at counts_ptr: partitions present and public,
+        present and not public, public and not present."""
+        st = self.lib.dpg_partition_summary(self.handle, pk_ptr, int(n), int(n_partitions),
+                                            public_mask_ptr, counts_ptr, stream)
+        self.check(st, "dpg_partition_summary")
 
     def stage_times(self):
         names = ctypes.create_string_buffer(4096)

@@ -8,3 +8,6 @@ from pipelinedp_amd.analysis import metrics
 from pipelinedp_amd.analysis.utility_analysis import perform_utility_analysis
 from pipelinedp_amd.analysis.utility_analysis import UtilityAnalysis
 from pipelinedp_amd.analysis import parameter_tuning
+from pipelinedp_amd.analysis import dataset_summary
+from pipelinedp_amd.analysis import pre_aggregation
+from pipelinedp_amd.analysis.pre_aggregation import preaggregate

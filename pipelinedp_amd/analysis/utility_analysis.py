@@ -7,10 +7,12 @@ bounder becomes a per-(privacy id, partition) pre-aggregation
 (analysis/contribution_bounders.py:37-77), the compound combiner holds one
 set of per-partition utility combiners per configuration
 (utility_analysis_engine.py:98-143) and private selection becomes a
-keep-probability computation.  On MI355X that is two C-ABI calls:
+keep-probability computation.  On MI355X that is two C-ABI calls (three with
+partitions_sampling_prob < 1 over integer keys):
 
   dpg_preaggregate      all (pid, pk) pairs with (count, sum, n_partitions,
                         n_contributions), sorted by partition key
+  dpg_sample_partitions the bitmap of the partitions the sampler keeps
   dpg_utility_analysis  every configuration's per-partition combiners in one
                         pass over the pairs (lane = configuration)
 
@@ -202,6 +204,13 @@ class UtilityAnalysis:
         if prob >= 1:
             return None
         bound = _sample_bound(prob)
+        if pre_aggregation.integer_keys(key_table):
+            # integer keys: hashed on the device (dpg_sample_partitions), the
+            # same decisions bit for bit; only the unpacked mask comes back
+            mask = pre_aggregation.device_sample_mask(self.backend, dev, P, key_table,
+                                                      self.owned, bound)
+            self.sampled = np.unpackbits(mask.cpu().numpy(), bitorder="little")[:P].astype(bool)
+            return mask
         # several ranks: the hash of the global keys of the owned ids only
         keys = columnar.decode_keys(self._global_ids(np.arange(P)), key_table)
         keep = np.array([_keep_by_hash(k, bound) for k in keys], bool)

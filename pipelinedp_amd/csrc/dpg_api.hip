@@ -73,6 +73,7 @@ static hipError_t set_func_attr(const void *kern, hipFuncAttribute attr, int val
 #include "dpg_quantile.h"
 #include "dpg_records.h"
 #include "dpg_rsort.h"
+#include "dpg_sample.h"
 #include "dpg_select.h"
 #include "dpg_shard.h"
 #include "dpg_sortb.h"
@@ -2653,6 +2654,82 @@ int dpg_hist_sums(dpg_ctx *ctx, const dpg_pair_entry *pairs, int64_t n_pairs,
         LAUNCH_CHECK();
     }
     stage(ctx, s, "hist.end");
+    return DPG_OK;
+}
+
+// The partition sampler (dpg_sample.h): stream-ordered, no host
+// synchronisation.  It appends its stage to the running list (it runs between
+// dpg_preaggregate and dpg_utility_analysis, which continues that list).
+int dpg_sample_partitions(dpg_ctx *ctx, const int64_t *keys, int64_t key_lo, int64_t key_stride,
+                          int64_t n, uint64_t bound, int32_t keep_all, uint8_t *mask,
+                          uint64_t *hashes, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (!mask || n < 0) return fail(ctx, DPG_ERR_INVALID_ARG, "null mask or negative n");
+    if ((reinterpret_cast<uintptr_t>(mask) & 7) || (reinterpret_cast<uintptr_t>(hashes) & 7) ||
+        (reinterpret_cast<uintptr_t>(keys) & 7))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "mask, hashes and keys must be 8-byte aligned");
+    (void)hipSetDevice(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    ctx->last_stream = s;
+    // a sampler call right behind another takes over its two entries: a loop
+    // of calls does not grow the list
+    if (ctx->n_events_used >= 2 && ctx->stage_names.size() >= 2 &&
+        ctx->stage_names.back() == "ua.sampled") {
+        ctx->n_events_used -= 2;
+        ctx->stage_names.resize(ctx->stage_names.size() - 2);
+    }
+    stage(ctx, s, "ua.sample");
+    if (n > 0) {
+        const unsigned g = (unsigned)std::min<int64_t>(
+            (n + kSampleThreads - 1) / kSampleThreads, (int64_t)ctx->n_cu * 64);
+        k_sample_partitions<<<g, kSampleThreads, 0, s>>>(
+            keys, (uint64_t)key_lo, (uint64_t)key_stride, n, bound, keep_all != 0,
+            reinterpret_cast<unsigned long long *>(mask),
+            reinterpret_cast<unsigned long long *>(hashes));
+        LAUNCH_CHECK();
+    }
+    stage(ctx, s, "ua.sampled");
+    return DPG_OK;
+}
+
+// PublicPartitionsSummary's three counts (dpg_sample.h).  Synchronises the
+// stream once, to report keys outside [0, P).
+int dpg_partition_summary(dpg_ctx *ctx, const int64_t *pk, int64_t n, int64_t P,
+                          const uint8_t *public_mask, int64_t *counts, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (!public_mask || !counts || n < 0 || (n > 0 && !pk))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "null argument");
+    if (P <= 0 || P >= 0xFFFFFFFFll)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "n_partitions must be in [1, 2^32-1)");
+    if (reinterpret_cast<uintptr_t>(counts) & 7)
+        return fail(ctx, DPG_ERR_INVALID_ARG, "counts must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    int st = hist_begin(ctx, s);
+    stage(ctx, s, "summary.mark");
+    WS(present, uint8_t, "summary.present", P);
+    WS(bad, uint32_t, "summary.bad", 1);
+    HIP_TRY(hipMemsetAsync(present, 0, (size_t)P, s));
+    HIP_TRY(hipMemsetAsync(bad, 0, 4, s));
+    HIP_TRY(hipMemsetAsync(counts, 0, 3 * 8, s));
+    if (n > 0) {
+        k_summary_mark<<<(unsigned)std::min<int64_t>((n + kSummaryThreads - 1) / kSummaryThreads,
+                                                     (int64_t)ctx->n_cu * 16),
+                         kSummaryThreads, 0, s>>>(pk, n, P, present, bad);
+        LAUNCH_CHECK();
+    }
+    stage(ctx, s, "summary.count");
+    k_summary_count<<<(unsigned)std::min<int64_t>((P + kSummaryThreads - 1) / kSummaryThreads,
+                                                  (int64_t)ctx->n_cu * 16),
+                      kSummaryThreads, 0, s>>>(present, public_mask, P,
+                                               reinterpret_cast<unsigned long long *>(counts));
+    LAUNCH_CHECK();
+    stage(ctx, s, "summary.end");
+    uint32_t hbad = 0;
+    HIP_TRY(hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (hbad)
+        return fail(ctx, DPG_ERR_KEY_RANGE,
+                    "partition key outside [0, n_partitions=" + std::to_string(P) + ")");
     return DPG_OK;
 }
 

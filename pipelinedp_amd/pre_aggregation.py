@@ -138,6 +138,41 @@ def host_preaggregated_pairs(col, extractors, public_partitions, dev) -> PairSet
     return PairSet(pairs, torch.from_numpy(starts).to(dev), P, n, table, pub_mask)
 
 
+def integer_keys(key_table) -> bool:
+    """The partition keys are integers whose repr is their decimal form:
+    dense ids (no key table) or an integer ndarray table (integer columns).
+    Anything else -- strings, tuples, np.generic row keys, whose repr is
+    "np.int64(5)" -- is hashed on the host."""
+    if key_table is None:
+        return True
+    return (isinstance(key_table, np.ndarray) and
+            (key_table.dtype.kind == "i" or
+             (key_table.dtype.kind == "u" and key_table.dtype.itemsize < 8)))
+
+
+def device_sample_mask(backend, dev, n: int, key_table, owned, bound: int) -> torch.Tensor:
+    """The partition sampler's bitmap (dpg_sample_partitions) of the n
+    partitions of a PairSet with integer keys: device uint8[8 * ceil(n / 64)],
+    bit i set iff the sampler keeps partition i's key under `bound`
+    (round(2^64 * p), up to 2^64).  owned: the (lo, stride, n) slice of the
+    dense ids this rank holds under local ids, or None.  No host object of
+    size n is built, and nothing waits for the device."""
+    lo, stride = (0, 1) if owned is None else owned[:2]
+    keys = None
+    if key_table is not None:
+        table = torch.from_numpy(np.ascontiguousarray(key_table, dtype=np.int64)).to(dev)
+        keys = table if owned is None else table[lo::stride][:n].contiguous()
+        if keys.numel() < n:  # an empty table still declares one (empty) partition
+            keys = torch.cat([keys, keys.new_zeros(n - keys.numel())])
+    mask = torch.empty(8 * max((n + 63) // 64, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        sptr = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        backend.ctx.sample_partitions(
+            ctypes.c_void_p(keys.data_ptr()) if keys is not None else None, lo, stride, n, bound,
+            ctypes.c_void_p(mask.data_ptr()), None, sptr)
+    return mask
+
+
 def to_numpy(ps: PairSet) -> np.ndarray:
     """The pairs as a structured host array (tests, reports)."""
     a = ps.pairs[:ps.n_pairs].cpu().numpy()
