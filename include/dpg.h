@@ -555,6 +555,56 @@ int dpg_owner_split_keys(dpg_ctx *ctx, const uint64_t *keys, const int64_t *n_ke
                          uint64_t *out_keys, uint32_t *out_src, int64_t *counts,
                          void *stream);
 
+/* ---- sparse partition keys: a write-once hash dictionary on the device ----
+ * Partition keys that are not dense ids (hashes, timestamps, product ids) get
+ * global dense ids from a dictionary built over every rank's distinct keys
+ * (distributed.build_key_dictionary; csrc/dpg_keydict.h).  The four calls
+ * below are its device side: the distinct keys of a record column by one
+ * probe per record, their compaction, and the id of every record once the
+ * distinct keys have theirs.
+ *
+ * The table is the caller's: slots (device uint64[capacity], capacity a power
+ * of two in [64, 2^31]) filled with DPG_KEYDICT_EMPTY before the first
+ * insert, and slot_ids (device uint32[capacity], any content).  A slot goes
+ * from DPG_KEYDICT_EMPTY to a key once and never changes again.  The key
+ * INT64_MIN has the bit pattern of DPG_KEYDICT_EMPTY: it is reserved, counted
+ * and never inserted.
+ *   h     = fmix64(key)       murmur3's finaliser on the key's 64 bits:
+ *                             k ^= k >> 33; k *= 0xff51afd7ed558ccd;
+ *                             k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53; k ^= k >> 33
+ *   home  = h & (capacity - 1), linear probing with wrap-around
+ *   owner = ((h >> 32) * nranks) >> 32     (host side: distributed.key_owner)
+ * Every probe sequence ends after at most `capacity` steps.
+ *
+ * All four: n < 2^31 (else DPG_ERR_UNSUPPORTED); n == 0 is a no-op (the
+ * per-record pointers may then be NULL); a bad capacity, n < 0 or a NULL
+ * pointer: DPG_ERR_INVALID_ARG; both before any device work.  The counters
+ * are added to, so the caller zeroes them.  Stream-ordered, no host
+ * synchronisation. */
+#define DPG_KEYDICT_EMPTY 0x8000000000000000ull
+/* Inserts the distinct values of keys[0, n).  info (device int64[2]):
+ * info[0] += records holding the reserved key, info[1] += records that found
+ * no slot (the table is full: with capacity >= 2 x the distinct keys this
+ * stays 0).  May be called several times on one table. */
+int dpg_keydict_insert(dpg_ctx *ctx, const int64_t *keys, int64_t n, uint64_t *slots,
+                       int64_t capacity, int64_t *info, void *stream);
+/* out_keys (device int64[capacity]) receives the keys of the occupied slots,
+ * in no particular order, *n_keys (device int64) their number. */
+int dpg_keydict_keys(dpg_ctx *ctx, const uint64_t *slots, int64_t capacity, int64_t *out_keys,
+                     int64_t *n_keys, void *stream);
+/* slot_ids[slot of keys[i]] = ids[i] for i < n (ids: device int64, every value
+ * in [0, 2^32 - 1); equal keys must carry equal ids).  *n_missing (device
+ * int64) += the keys that are not in the table, the reserved key included. */
+int dpg_keydict_assign(dpg_ctx *ctx, const int64_t *keys, const int64_t *ids, int64_t n,
+                       const uint64_t *slots, uint32_t *slot_ids, int64_t capacity,
+                       int64_t *n_missing, void *stream);
+/* out_ids[i] (device int64[n]) = the id assigned to keys[i]; a key that is
+ * absent or reserved gives -1 and *n_missing (device int64) += 1.  The id of
+ * a key that is present but was never assigned is unspecified. */
+int dpg_keydict_lookup(dpg_ctx *ctx, const int64_t *keys, int64_t n, const uint64_t *slots,
+                       const uint32_t *slot_ids, int64_t capacity, int64_t *out_ids,
+                       int64_t *n_missing, void *stream);
+
 /* ---- multi-GPU utility analysis: pairs to the rank that owns their partition ----
  * The per-partition utility combiners need every (privacy id, partition) pair
  * of a partition on one rank, so each rank's pre-aggregate travels to the

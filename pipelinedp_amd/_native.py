@@ -27,7 +27,11 @@ EXPORTED = ("dpg_ctx_create", "dpg_ctx_destroy", "dpg_last_error", "dpg_set_seed
             "dpg_owner_split_keys", "dpg_owner_split_pairs", "dpg_merge_pair_runs",
             "dpg_sort_pairs_u64", "dpg_bound_records", "dpg_quantile_keys", "dpg_quantiles",
             "dpg_vector_index", "dpg_vector_sums", "dpg_vector_clip_noise",
-            "dpg_sample_partitions", "dpg_partition_summary")
+            "dpg_sample_partitions", "dpg_partition_summary",
+            "dpg_keydict_insert", "dpg_keydict_keys", "dpg_keydict_assign",
+            "dpg_keydict_lookup")
+
+KEYDICT_EMPTY = 1 << 63  # DPG_KEYDICT_EMPTY: the bit pattern of INT64_MIN, the reserved key
 
 COMM_ID_BYTES = 128  # DPG_COMM_ID_BYTES
 
@@ -272,6 +276,14 @@ def load():
         lib.dpg_sample_partitions.restype = ctypes.c_int
         lib.dpg_partition_summary.argtypes = [vp, vp, i64, i64, vp, vp, vp]
         lib.dpg_partition_summary.restype = ctypes.c_int
+        lib.dpg_keydict_insert.argtypes = [vp, vp, i64, vp, i64, vp, vp]
+        lib.dpg_keydict_insert.restype = ctypes.c_int
+        lib.dpg_keydict_keys.argtypes = [vp, vp, i64, vp, vp, vp]
+        lib.dpg_keydict_keys.restype = ctypes.c_int
+        lib.dpg_keydict_assign.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp, vp]
+        lib.dpg_keydict_assign.restype = ctypes.c_int
+        lib.dpg_keydict_lookup.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, vp]
+        lib.dpg_keydict_lookup.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -549,6 +561,38 @@ class Context:
         st = self.lib.dpg_partition_summary(self.handle, pk_ptr, int(n), int(n_partitions),
                                             public_mask_ptr, counts_ptr, stream)
         self.check(st, "dpg_partition_summary")
+
+    def keydict_insert(self, keys_ptr, n, slots_ptr, capacity, info_ptr, stream):
+        """Inserts the distinct values of n int64 keys into the write-once
+        table slots (device uint64[capacity], filled with KEYDICT_EMPTY);
+        info (device int64[2]) += (records with the reserved key INT64_MIN,
+        records that found no slot)."""
+        st = self.lib.dpg_keydict_insert(self.handle, keys_ptr, int(n), slots_ptr, int(capacity),
+                                         info_ptr, stream)
+        self.check(st, "dpg_keydict_insert")
+
+    def keydict_keys(self, slots_ptr, capacity, out_keys_ptr, n_keys_ptr, stream):
+        """The occupied slots' keys, compacted into out_keys (device
+        int64[capacity], unspecified order); their count at n_keys_ptr."""
+        st = self.lib.dpg_keydict_keys(self.handle, slots_ptr, int(capacity), out_keys_ptr,
+                                       n_keys_ptr, stream)
+        self.check(st, "dpg_keydict_keys")
+
+    def keydict_assign(self, keys_ptr, ids_ptr, n, slots_ptr, slot_ids_ptr, capacity,
+                       n_missing_ptr, stream):
+        """slot_ids[slot of keys[i]] = ids[i] (device int64, < 2^32 - 1); the
+        device int64 at n_missing_ptr += keys that are not in the table."""
+        st = self.lib.dpg_keydict_assign(self.handle, keys_ptr, ids_ptr, int(n), slots_ptr,
+                                         slot_ids_ptr, int(capacity), n_missing_ptr, stream)
+        self.check(st, "dpg_keydict_assign")
+
+    def keydict_lookup(self, keys_ptr, n, slots_ptr, slot_ids_ptr, capacity, out_ids_ptr,
+                       n_missing_ptr, stream):
+        """out_ids[i] (device int64) = the id assigned to keys[i], -1 for an
+        absent or reserved key, which the device int64 at n_missing_ptr counts."""
+        st = self.lib.dpg_keydict_lookup(self.handle, keys_ptr, int(n), slots_ptr, slot_ids_ptr,
+                                         int(capacity), out_ids_ptr, n_missing_ptr, stream)
+        self.check(st, "dpg_keydict_lookup")
 
     def stage_times(self):
         names = ctypes.create_string_buffer(4096)

@@ -48,7 +48,19 @@ class ColumnarData:
     ValueError if any rank holds a record it does not own); "shuffle": the
     records are split any way at all and are exchanged before bounding
     (record_id_offset is then ignored; a privacy_id_range must be global).
-    "verify" and "shuffle" need integer privacy ids."""
+    "verify" and "shuffle" need integer privacy ids.
+
+    `sparse_partition_keys` (opt-in): `pk` holds any int64 values but
+    INT64_MIN -- hashes, timestamps, product ids -- and the device builds the
+    dictionary that gives them dense ids, the same on every rank
+    (distributed.build_key_dictionary).  This is how
+    several ranks take keys that are not dense ids; one process runs the same
+    kernels.  `pk` and the public partitions must then be integers, the public
+    partitions the same on every rank, and `n_partitions` must not be given.
+    Results carry the caller's keys.  `max_distinct_partition_keys`: an upper
+    bound on one rank's distinct partition keys, public ones included, which
+    sizes the hash table (else the record count does); a bound that is too
+    small raises ValueError on every rank."""
     pid: Any = None
     pk: Any = None
     value: Any = None
@@ -56,10 +68,15 @@ class ColumnarData:
     privacy_id_range: Optional[Tuple[int, int]] = None
     record_id_offset: int = 0
     sharding: str = "trusted"
+    sparse_partition_keys: bool = False
+    max_distinct_partition_keys: Optional[int] = None
 
     def __post_init__(self):
         if self.sharding not in SHARDING_MODES:
             raise ValueError(f"sharding must be one of {SHARDING_MODES}, got {self.sharding!r}")
+        if self.sparse_partition_keys and self.n_partitions is not None:
+            raise ValueError("sparse_partition_keys=True builds the dense partition ids itself: "
+                             "n_partitions must not be given")
 
     def __getitem__(self, name):
         return getattr(self, name)
@@ -89,6 +106,11 @@ class EncodedInput:
     # encoding (which differs from rank to rank): shard_of(pid) is global
     pid_unencoded: bool = False
     pid_range_declared: bool = False  # pid_min / pid_count come from privacy_id_range
+    # sparse_partition_keys: pk still holds the caller's int64 keys (and
+    # public_keys the public ones) until distributed.build_key_dictionary
+    # replaces them by global dense ids
+    pk_sparse: bool = False
+    public_keys: Optional[torch.Tensor] = None
 
 
 def _extract(col, extractor):
@@ -166,6 +188,23 @@ def _public_id_tensor(public_partitions, device) -> Optional[torch.Tensor]:
     return None
 
 
+def _sparse_public_keys(public_partitions, device) -> torch.Tensor:
+    """The public partitions of a sparse_partition_keys input as a device
+    int64 tensor: an integer range, list, array or tensor; else TypeError."""
+    t = _public_id_tensor(public_partitions, device)
+    if t is None and isinstance(public_partitions, (list, tuple)) and all(
+            _is_int_key(k) for k in public_partitions):
+        try:
+            t = torch.from_numpy(np.asarray(public_partitions, dtype=np.int64)
+                                 .reshape(-1)).to(device)
+        except OverflowError:
+            t = None
+    if t is None:
+        raise TypeError("sparse_partition_keys=True needs integer public partitions: a range, "
+                        "list, array or tensor of int64 keys, the same on every rank")
+    return t
+
+
 def _check_public_range(lo: int, hi: int, P: int) -> None:
     if lo < 0 or hi >= P:
         raise ValueError(
@@ -214,7 +253,8 @@ def _range(t: torch.Tensor):
 
 
 def encode(col, extractors, device: torch.device, need_values: bool,
-           public_partitions=None, need_pid: bool = True) -> EncodedInput:
+           public_partitions=None, need_pid: bool = True,
+           allow_sparse: bool = False) -> EncodedInput:
     pid_range, rec_off = None, 0
     if _is_columnar(col):
         pid = _extract(col, extractors.privacy_id_extractor) if need_pid else None
@@ -247,8 +287,25 @@ def encode(col, extractors, device: torch.device, need_values: bool,
             pub_range = (public_partitions.start, public_partitions.stop)
         else:
             pub_dense = _public_id_tensor(public_partitions, device)
+    # ColumnarData(sparse_partition_keys=True): the keys stay as they are and
+    # DeviceAggregation builds their dictionary (every rank the same one)
+    sparse = isinstance(col, ColumnarData) and col.sparse_partition_keys
+    sparse_public = None
+    if sparse:
+        if not allow_sparse:  # the analysis, histogram and tune entry points
+            raise NotImplementedError(
+                "sparse_partition_keys=True is supported by DPEngine.aggregate (COUNT, SUM, "
+                "PRIVACY_ID_COUNT, MEAN, VARIANCE) and select_partitions only")
+        if hint is not None:
+            raise ValueError("sparse_partition_keys=True builds the dense partition ids itself: "
+                             "n_partitions must not be given")
+        if not _integer_like(pk):
+            raise TypeError("sparse_partition_keys=True needs an integer tensor or array of "
+                            "partition keys")
+        if public_partitions is not None:
+            sparse_public = _sparse_public_keys(public_partitions, device)
     public_list = (None if public_partitions is None or pub_dense is not None
-                   or pub_range is not None else list(public_partitions))
+                   or pub_range is not None or sparse else list(public_partitions))
     key_table = None
     pk_ids = None
     public_ids = None
@@ -258,11 +315,13 @@ def encode(col, extractors, device: torch.device, need_values: bool,
     # Only without an n_partitions hint: with one, the keys are the caller's
     # dense ids, and the public bitmap above (pub_range / pub_dense) was
     # built over those ids, so they must not be re-encoded
-    np_row_keys = (hint is None and isinstance(pk, list)
+    np_row_keys = (hint is None and not sparse and isinstance(pk, list)
                    and any(isinstance(k, np.generic) for k in pk))
     if _integer_like(pk) and not np_row_keys:
         pk_t = _to_tensor(pk, device).to(torch.int64)
-        if hint is not None:
+        if sparse:
+            pk_ids, P = pk_t, 1  # P: a placeholder until the dictionary is built
+        elif hint is not None:
             P = int(hint)
             pk_ids = pk_t
             if public_list is not None:
@@ -327,7 +386,8 @@ def encode(col, extractors, device: torch.device, need_values: bool,
                        pid_count=pid_count, rec_id_offset=rec_off,
                        partitions_declared=hint is not None and key_table is None,
                        pid_unencoded=pid_unencoded,
-                       pid_range_declared=pid_unencoded and pid_range is not None)
+                       pid_range_declared=pid_unencoded and pid_range is not None,
+                       pk_sparse=bool(sparse), public_keys=sparse_public)
     if pub_range is not None:
         enc.public_mask, enc.public_count = _range_bitmap(*pub_range, int(P), device)
     elif pub_dense is not None:

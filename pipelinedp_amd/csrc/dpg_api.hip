@@ -67,6 +67,7 @@ static hipError_t set_func_attr(const void *kern, hipFuncAttribute attr, int val
 #include "dpg_chunk.h"
 #include "dpg_common.h"
 #include "dpg_hist.h"
+#include "dpg_keydict.h"
 #include "dpg_owner.h"
 #include "dpg_pairx.h"
 #include "dpg_partition.h"
@@ -3043,6 +3044,86 @@ int dpg_owner_split_keys(dpg_ctx *ctx, const uint64_t *keys, const int64_t *n_ke
     LAUNCH_CHECK();
     stage(ctx, s, "owner:end");
     return st;
+}
+
+// ---- sparse partition keys: the write-once key dictionary (dpg_keydict.h)
+static const char *keydict_table_error(const void *slots, int64_t capacity) {
+    if (!slots) return "slots is NULL";
+    if (capacity < 64 || capacity > 0x80000000ll || (capacity & (capacity - 1)))
+        return "capacity must be a power of two in [64, 2^31]";
+    return nullptr;
+}
+
+static unsigned keydict_blocks(const dpg_ctx *ctx, int64_t n) {
+    return (unsigned)std::min<int64_t>((n + kKdThreads - 1) / kKdThreads, (int64_t)ctx->n_cu * 8);
+}
+
+int dpg_keydict_insert(dpg_ctx *ctx, const int64_t *keys, int64_t n, uint64_t *slots,
+                       int64_t capacity, int64_t *info, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (const char *e = keydict_table_error(slots, capacity)) return fail(ctx, DPG_ERR_INVALID_ARG, e);
+    if (n < 0 || !info || (n > 0 && !keys))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "n < 0, or keys or info is NULL");
+    if (n >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n must be < 2^31 per device");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) return DPG_OK;
+    k_keydict_insert<<<keydict_blocks(ctx, n), kKdThreads, 0, s>>>(
+        reinterpret_cast<const uint64_t *>(keys), (uint32_t)n, slots, (uint32_t)(capacity - 1),
+        reinterpret_cast<unsigned long long *>(info));
+    LAUNCH_CHECK();
+    return DPG_OK;
+}
+
+int dpg_keydict_keys(dpg_ctx *ctx, const uint64_t *slots, int64_t capacity, int64_t *out_keys,
+                     int64_t *n_keys, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (const char *e = keydict_table_error(slots, capacity)) return fail(ctx, DPG_ERR_INVALID_ARG, e);
+    if (!out_keys || !n_keys) return fail(ctx, DPG_ERR_INVALID_ARG, "out_keys or n_keys is NULL");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(n_keys, 0, 8, s));
+    k_keydict_keys<<<keydict_blocks(ctx, capacity), kKdThreads, 0, s>>>(
+        slots, (uint32_t)capacity, reinterpret_cast<uint64_t *>(out_keys),
+        reinterpret_cast<unsigned long long *>(n_keys));
+    LAUNCH_CHECK();
+    return DPG_OK;
+}
+
+int dpg_keydict_assign(dpg_ctx *ctx, const int64_t *keys, const int64_t *ids, int64_t n,
+                       const uint64_t *slots, uint32_t *slot_ids, int64_t capacity,
+                       int64_t *n_missing, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (const char *e = keydict_table_error(slots, capacity)) return fail(ctx, DPG_ERR_INVALID_ARG, e);
+    if (n < 0 || !slot_ids || !n_missing || (n > 0 && (!keys || !ids)))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "n < 0, or keys, ids, slot_ids or n_missing is NULL");
+    if (n >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n must be < 2^31 per device");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) return DPG_OK;
+    k_keydict_assign<<<keydict_blocks(ctx, n), kKdThreads, 0, s>>>(
+        reinterpret_cast<const uint64_t *>(keys), ids, (uint32_t)n, slots, slot_ids,
+        (uint32_t)(capacity - 1), reinterpret_cast<unsigned long long *>(n_missing));
+    LAUNCH_CHECK();
+    return DPG_OK;
+}
+
+int dpg_keydict_lookup(dpg_ctx *ctx, const int64_t *keys, int64_t n, const uint64_t *slots,
+                       const uint32_t *slot_ids, int64_t capacity, int64_t *out_ids,
+                       int64_t *n_missing, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (const char *e = keydict_table_error(slots, capacity)) return fail(ctx, DPG_ERR_INVALID_ARG, e);
+    if (n < 0 || !slot_ids || !n_missing || (n > 0 && (!keys || !out_ids)))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "n < 0, or keys, slot_ids, out_ids or n_missing is NULL");
+    if (n >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n must be < 2^31 per device");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) return DPG_OK;
+    k_keydict_lookup<<<keydict_blocks(ctx, n), kKdThreads, 0, s>>>(
+        reinterpret_cast<const uint64_t *>(keys), (uint32_t)n, slots, slot_ids,
+        (uint32_t)(capacity - 1), out_ids, reinterpret_cast<unsigned long long *>(n_missing));
+    LAUNCH_CHECK();
+    return DPG_OK;
 }
 
 static bool ranges_overlap(const void *a, const void *b, size_t bytes);

@@ -70,7 +70,8 @@ def check_dropped(block: bool = False) -> None:
 
 
 class DeviceResult:
-    """Materialised result: kept partition ids (int64 [K], global dense ids)
+    """Materialised result: kept partition ids (int64 [K], global dense ids;
+    with ColumnarData(sparse_partition_keys=True) the caller's int64 keys)
     and their metric columns (float64 [K, len(fields)]), on the device; with
     VECTOR_SUM the last field `vector_sum` takes the last vector_size columns
     ([K, n_scalar + D]).  `keys()` maps ids back to the user's partition keys.
@@ -81,8 +82,11 @@ class DeviceResult:
 
     def __init__(self, partition_ids: torch.Tensor, values: torch.Tensor, fields: tuple,
                  key_table: Optional[Sequence], stage_ms: Optional[dict] = None,
-                 pending: Optional[tuple] = None):
+                 pending: Optional[tuple] = None, key_map: Optional[torch.Tensor] = None):
         self._ids, self._vals = partition_ids, values
+        # sparse partition keys: the kept local ids index this int64 tensor of
+        # the caller's keys (the rank's owned keys) instead of being re-based
+        self._key_map = key_map
         self.fields = fields
         self.key_table = key_table
         self.stage_ms = stage_ms if stage_ms is not None else {}
@@ -104,7 +108,9 @@ class DeviceResult:
             raise _native.NativeError(
                 "dpg_compact_kept failed (HIP error): internal hash-table error in bounding")
         ids = self._ids[:k]
-        if stride != 1 or offset:  # several ranks: this rank's slice
+        if self._key_map is not None:
+            ids = self._key_map[ids]
+        elif stride != 1 or offset:  # several ranks: this rank's slice
             ids = ids * stride + offset
         vals = (self._vals[:k * n_out].view(k, n_out) if n_out
                 else torch.empty((k, 0), dtype=torch.float64, device=self._vals.device))
@@ -171,6 +177,8 @@ class DeviceAggregation:
         self.last_bound_fields: Optional[dict] = None
         self.last_exchange: Optional[dict] = None
         self.last_select_fields: Optional[dict] = None
+        # sparse_partition_keys: the distributed.KeyDictionary of the release
+        self.last_key_dictionary = None
 
     # ------------------------------------------------------------ public
     def __iter__(self):
@@ -257,6 +265,30 @@ class DeviceAggregation:
             return
         distributed.place_records(enc, self.backend, mode)
 
+    def _encode_sparse_keys(self, enc) -> None:
+        """ColumnarData(sparse_partition_keys=True): replaces the caller's
+        int64 partition keys in `enc` by global dense ids, the same on every
+        rank (distributed.build_key_dictionary: the hash-dictionary kernels,
+        with several ranks four collectives), before the records are placed.
+        The public bitmap is built over the public keys' ids; the result maps
+        the kept local ids back through this rank's owned keys."""
+        backend = self.backend
+        dev = backend.device
+        group = backend.process_group if backend.world_size > 1 else None
+        with torch.cuda.device(dev):
+            sptr = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            kd = distributed.build_key_dictionary(
+                enc.pk, enc.public_keys, group, backend.ctx, sptr,
+                max_distinct=self.col.max_distinct_partition_keys)
+            enc.pk = kd.ids
+            enc.n_partitions = kd.n_partitions
+            enc.partitions_declared = True
+            enc.pk_sparse = False
+            if kd.public_ids is not None:
+                enc.public_mask, enc.public_count = columnar._device_bitmap(
+                    kd.public_ids, kd.n_partitions, dev)
+        self.last_key_dictionary = kd
+
     def _own_quantile_keys(self, qkeys, n_qkeys, local_P: int, sptr):
         """Several ranks: this rank's sorted tree keys pk << 16 | leaf go to
         their partitions' owners (distributed.exchange_owner_keys: one split,
@@ -310,9 +342,19 @@ class DeviceAggregation:
         ctx = backend.ctx
         dev = backend.device
         need_values = self.plan is not None and self.plan.needs_values()
+        sparse = isinstance(self.col, columnar.ColumnarData) and self.col.sparse_partition_keys
+        if sparse and self.plan is not None and (self.plan.percentiles
+                                                  or self.plan.vector_size is not None):
+            # host state only: every rank raises alike, before any collective
+            raise NotImplementedError(
+                "sparse_partition_keys=True supports COUNT, SUM, PRIVACY_ID_COUNT, MEAN and "
+                "VARIANCE; PERCENTILE and VECTOR_SUM need dense partition ids "
+                "(ColumnarData(n_partitions=P))")
         enc = columnar.encode(self.col, self.extractors, dev, need_values,
                               self.public_partitions,
-                              need_pid=not self.bounds_already_enforced)
+                              need_pid=not self.bounds_already_enforced, allow_sparse=True)
+        if enc.pk_sparse:
+            self._encode_sparse_keys(enc)
         if self.bounds_already_enforced:
             enc.pid = torch.arange(enc.n, dtype=torch.int64, device=dev)
             enc.pid_min, enc.pid_count = 0, max(1, enc.n)
@@ -475,10 +517,21 @@ class DeviceAggregation:
                                   ids.data_ptr(), kept_out.data_ptr(), info.data_ptr(), sptr)
             done = torch.cuda.Event()
             done.record(stream)
+            # sparse partition keys: the owner turns its kept local ids into the
+            # caller's keys (its slice of the dictionary; no global key table)
+            kd = self.last_key_dictionary if sparse else None
+            key_map = None
+            if kd is not None:
+                # local_P entries: the ids past this owner's keys are holes,
+                # never public and never occupied, so never kept
+                key_map = torch.zeros(local_P, dtype=torch.int64, device=dev)
+                key_map[:kd.owned_keys.numel()] = kd.owned_keys
             res = DeviceResult(ids, kept_out, fields, enc.key_table, stage_ms,
-                               pending=(info, n_out, pk_stride, pk_offset, done))
+                               pending=(info, n_out, pk_stride, pk_offset, done),
+                               key_map=key_map)
             if backend.world_size > 1 and gather:
                 ids, vals = distributed.all_gather_results(res.partition_ids, res.values,
-                                                           backend.process_group)
+                                                           backend.process_group,
+                                                           exact_ids=kd is not None)
                 res = DeviceResult(ids, vals, fields, enc.key_table, stage_ms)
         return res

@@ -84,12 +84,21 @@ The integer accumulators travel as float64, exact below 2^53 (a rank holds
 the collectives are staged through host memory and the reduce-scatter is an
 all_reduce + slice.
 
+Partition keys that are not dense ids (ColumnarData(sparse_partition_keys=
+True): any int64 but INT64_MIN) get them first: `build_key_dictionary` reduces
+each rank's records to their distinct keys in a write-once hash table on the
+device, sends those to the ranks `key_owner` names, numbers them there so that
+id % R is that owner, and maps every record through the table (DESIGN.md
+section 16).  The kept results then carry the caller's keys
+(`all_gather_results(exact_ids=True)`).
+
 Every random draw is keyed by (stream seed, pid, pk) or (stream seed, pk)
 with global partition ids -- never by rank -- and the release nonce comes
 from rank 0, so the selected-partition set is identical for any world size
 (SURVEY.md 8(e)).
 """
 import ctypes
+import dataclasses
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -322,6 +331,208 @@ def exchange_owner_keys(keys: torch.Tensor, n_keys, low_bits: int, group, ctx=No
 
 DENSE_IDS_ERROR = ("multi-GPU aggregation needs globally dense integer partition ids: "
                    "pass ColumnarData(..., n_partitions=P) with pk in [0, P) on every rank")
+
+
+def _as_i64(c: int) -> int:
+    return c - (1 << 64) if c >= 1 << 63 else c
+
+
+def _lsr(x: torch.Tensor, bits: int) -> torch.Tensor:
+    """Logical shift right of int64 bit patterns."""
+    return (x >> bits) & ((1 << (64 - bits)) - 1)
+
+
+def key_hash(keys) -> torch.Tensor:
+    """fmix64 (murmur3's 64-bit finaliser) of int64 keys, as int64 bit
+    patterns: the hash of the device key dictionary (csrc/dpg_keydict.h), bit
+    for bit.  A key's home slot in a table of `capacity` slots is
+    key_hash(key) & (capacity - 1)."""
+    k = torch.as_tensor(keys).to(torch.int64)
+    k = k ^ _lsr(k, 33)
+    k = k * _as_i64(0xff51afd7ed558ccd)  # int64 products wrap: arithmetic mod 2^64
+    k = k ^ _lsr(k, 33)
+    k = k * _as_i64(0xc4ceb9fe1a85ec53)
+    return k ^ _lsr(k, 33)
+
+
+def key_owner(keys, world_size: int) -> torch.Tensor:
+    """Rank owning each sparse partition key: ((h >> 32) * R) >> 32 with h =
+    key_hash(key) -- the hash's high half, independent of the slot bits."""
+    return (_lsr(key_hash(keys), 32) * int(world_size)) >> 32
+
+
+@dataclasses.dataclass
+class KeyDictionary:
+    """What build_key_dictionary returns (see there)."""
+    ids: torch.Tensor                    # int64: the global dense id of every record
+    public_ids: Optional[torch.Tensor]   # the same for the public keys, or None
+    n_partitions: int                    # P, the same on every rank
+    owned_keys: torch.Tensor             # this rank's owned keys, int64, ascending
+    keys: torch.Tensor                   # this rank's distinct keys, ascending
+    key_ids: torch.Tensor                # their global ids
+
+
+def build_key_dictionary(pk: torch.Tensor, public_keys: Optional[torch.Tensor], group, ctx=None,
+                         stream=None, max_distinct: Optional[int] = None) -> KeyDictionary:
+    """Global dense ids for sparse int64 partition keys, the same on every rank.
+
+    pk: this rank's record keys (any int64 but INT64_MIN, which the device
+    table reserves); public_keys: the public partition keys, the same on every
+    rank, or None.  group: the process group; None = one process (R = 1, no
+    collective).
+
+    1. Local distinct keys.  Device tensors with the library context `ctx`:
+       one probe per record into a write-once hash table of capacity = the
+       power of two >= 2 * min(records + public keys, max_distinct), at least
+       64 (dpg_keydict_insert; 12 bytes per slot plus 8 for the compaction, so
+       max_distinct is what keeps the table small when the records outnumber
+       their keys), compacted (dpg_keydict_keys; reading the count back is
+       host synchronisation 1) and sorted ascending as signed values
+       (dpg_sort_pairs_u64 on key ^ 2^63).  Host tensors (the gloo CPU tests,
+       no context): torch.unique.
+    2. To owners: the sorted distinct keys are split by key_owner (torch ops:
+       the column is the distinct keys, not the records; reading the R counts
+       is host synchronisation 2), `_split_sizes` and one all_to_all_single.
+    3. At the owner: what arrived is sorted and adjacent duplicates dropped --
+       `owned_keys`; the key at position i gets the global id i * R + rank, so
+       id % R is its owner (owner_of) and id // R indexes owned_keys.  The ids
+       go back in arrival order with one all_to_all_single.
+    4. ONE all_reduce (sum) carries every rank's len(owned_keys) in a slot of
+       its own, the records holding the reserved key and the records that
+       found no slot.  P = R * max(len(owned_keys)) (at least R).  No rank
+       raises before this collective; after it all raise the same ValueError:
+       a reserved key, a table that overflowed (only with max_distinct; the
+       message names it), or P >= 2^32 - 1.
+    5. Map: dpg_keydict_assign stores the ids beside the rank's distinct keys
+       and dpg_keydict_lookup reads every record's and every public key's
+       (host tensors: searchsorted).  A key without an id is an internal error
+       (RuntimeError; its count is read back behind the lookups).
+
+    The ids between an owner's own key count and P / R are holes: no key has
+    them.  With R = 1 the ids are the ascending rank of each key, as
+    torch.unique(return_inverse=True) numbers them.  They depend only on the
+    union of the key sets and on R.  Every rank runs every collective (four:
+    the all_gather of `_split_sizes`, two all_to_all_single, one all_reduce),
+    a rank without records included."""
+    world = 1 if group is None else dist.get_world_size(group)
+    rank = 0 if group is None else dist.get_rank(group)
+    pk = pk.to(torch.int64).contiguous().view(-1)
+    dev = pk.device
+    if public_keys is not None:
+        public_keys = public_keys.to(torch.int64).to(dev).contiguous().view(-1)
+    n, m = pk.numel(), public_keys.numel() if public_keys is not None else 0
+    on_device = ctx is not None and dev.type == "cuda"
+    # ---- 1. local distinct keys, ascending
+    if on_device:
+        if stream is None:
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        bound = n + m if max_distinct is None else min(n + m, max(0, int(max_distinct)))
+        capacity = max(64, 1 << max(2 * bound - 1, 0).bit_length())
+        slots = torch.full((capacity,), _I64_MIN, dtype=torch.int64, device=dev)
+        info = torch.zeros(2, dtype=torch.int64, device=dev)
+        ctx.keydict_insert(pk.data_ptr(), n, slots.data_ptr(), capacity, info.data_ptr(), stream)
+        if m:
+            ctx.keydict_insert(public_keys.data_ptr(), m, slots.data_ptr(), capacity,
+                               info.data_ptr(), stream)
+        found = torch.empty(capacity, dtype=torch.int64, device=dev)
+        n_found = torch.empty(1, dtype=torch.int64, device=dev)
+        ctx.keydict_keys(slots.data_ptr(), capacity, found.data_ptr(), n_found.data_ptr(), stream)
+        cnt = int(n_found.item())  # host synchronisation 1
+        biased = found[:cnt] ^ _I64_MIN  # unsigned order of key ^ 2^63 = signed order of key
+        distinct = torch.empty_like(biased)
+        ctx.sort_pairs_u64(biased.data_ptr(), None, cnt, 0, 64, distinct.data_ptr(), None, stream)
+        distinct ^= _I64_MIN
+        del found, biased
+        errs = info
+    else:
+        both = pk if not m else torch.cat([pk, public_keys])
+        distinct = torch.unique(both)
+        n_reserved = int((both == _I64_MIN).sum().item())
+        distinct = distinct[distinct != _I64_MIN]
+        cnt = int(distinct.numel())
+        lost = 0
+        if max_distinct is not None:  # the device table's capacity, mirrored
+            capacity = max(64, 1 << max(2 * min(n + m, max(0, int(max_distinct))) - 1,
+                                        0).bit_length())
+            lost = max(0, cnt - capacity)
+        errs = torch.tensor([n_reserved, lost], dtype=torch.int64)
+    # ---- 2. to owners (ascending within a destination: the split is stable)
+    if world > 1:
+        dest = key_owner(distinct, world)
+        order = torch.argsort(dest, stable=True)
+        counts = torch.bincount(dest, minlength=world).cpu()  # host synchronisation 2
+        in_splits, out_splits = _split_sizes(counts, group, dev, "key dictionary", "keys")
+        arrived = _exchange_column(distinct[order], in_splits, out_splits, group)
+        # ---- 3. at the owner
+        total = int(arrived.numel())
+        if on_device:
+            biased = arrived ^ _I64_MIN
+            srt = torch.empty_like(biased)
+            ctx.sort_pairs_u64(biased.data_ptr(), None, total, 0, 64, srt.data_ptr(), None, stream)
+            owned_keys = torch.unique_consecutive(srt ^ _I64_MIN)
+        else:
+            owned_keys = torch.unique(arrived)
+        back = torch.searchsorted(owned_keys, arrived) * world + rank
+        got = _exchange_column(back, out_splits, in_splits, group)
+        key_ids = torch.empty_like(got)
+        key_ids[order] = got
+    else:
+        owned_keys = distinct
+        key_ids = torch.arange(cnt, dtype=torch.int64, device=dev)
+    # ---- 4. global size and errors
+    n_owned = int(owned_keys.numel())
+    if world > 1:
+        cdev = _coll_device(group, dev)
+        t = torch.zeros(world + 2, dtype=torch.int64, device=cdev)
+        t[rank] = n_owned
+        t[world:] = errs.to(cdev)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        t = t.tolist()
+        n_owned, n_reserved, n_lost = max(t[:world]), t[world], t[world + 1]
+    else:
+        n_reserved, n_lost = errs.tolist()
+    P = world * max(1, n_owned)
+    if n_reserved:
+        raise ValueError(
+            f"sparse partition keys: {n_reserved} records or public partitions hold the key "
+            f"INT64_MIN (-2^63), which the key dictionary reserves")
+    if n_lost:
+        raise ValueError(
+            f"sparse partition keys: the key dictionary sized by max_distinct={max_distinct} "
+            f"overflowed ({n_lost} records found no slot on their rank); raise max_distinct to at "
+            f"least the number of distinct partition keys of one rank")
+    if P >= (1 << 32) - 1:
+        raise ValueError(f"sparse partition keys: {P} partition ids; the kernels take fewer "
+                         f"than 2^32 - 1")
+    # ---- 5. map
+    if on_device:
+        slot_ids = torch.empty(capacity, dtype=torch.int32, device=dev)
+        n_missing = torch.zeros(1, dtype=torch.int64, device=dev)
+        ctx.keydict_assign(distinct.data_ptr(), key_ids.data_ptr(), cnt, slots.data_ptr(),
+                           slot_ids.data_ptr(), capacity, n_missing.data_ptr(), stream)
+        ids = torch.empty(n, dtype=torch.int64, device=dev)
+        ctx.keydict_lookup(pk.data_ptr(), n, slots.data_ptr(), slot_ids.data_ptr(), capacity,
+                           ids.data_ptr(), n_missing.data_ptr(), stream)
+        public_ids = None
+        if public_keys is not None:
+            public_ids = torch.empty(m, dtype=torch.int64, device=dev)
+            ctx.keydict_lookup(public_keys.data_ptr(), m, slots.data_ptr(), slot_ids.data_ptr(),
+                               capacity, public_ids.data_ptr(), n_missing.data_ptr(), stream)
+        missing = int(n_missing.item())
+    else:
+        def lookup(x):
+            pos = torch.searchsorted(distinct, x).clamp_(max=max(cnt - 1, 0))
+            hit = distinct[pos] == x if cnt else torch.zeros_like(x, dtype=torch.bool)
+            return (key_ids[pos] if cnt else torch.full_like(x, -1)), int((~hit).sum().item())
+        ids, missing = lookup(pk)
+        public_ids = None
+        if public_keys is not None:
+            public_ids, miss_pub = lookup(public_keys)
+            missing += miss_pub
+    if missing:
+        raise RuntimeError(f"key dictionary: {missing} keys have no id (internal error)")
+    return KeyDictionary(ids=ids, public_ids=public_ids, n_partitions=P, owned_keys=owned_keys,
+                         keys=distinct, key_ids=key_ids)
 
 
 def place_records(enc, backend, mode: str) -> None:
@@ -765,11 +976,13 @@ def slice_bitmap(mask: torch.Tensor, lo: int, stride: int, n: int) -> torch.Tens
     return (padded.view(-1, 8).to(torch.int64) * weights).sum(1).to(torch.uint8)
 
 
-def all_gather_results(ids: torch.Tensor, vals: torch.Tensor, group):
+def all_gather_results(ids: torch.Tensor, vals: torch.Tensor, group, exact_ids: bool = False):
     """Concatenates every rank's kept (ids, values) in rank order: one size
     exchange, then one all_gather of ids and values packed as float64 rows
-    (ids < 2^53 are exact).  Runs after dpg_compact_kept, which has already
-    synchronised the host."""
+    (ids < 2^53 are exact).  exact_ids: the ids are the caller's sparse int64
+    keys, which a float64 does not hold: they travel in an int64 all_gather of
+    their own.  Runs after dpg_compact_kept, which has already synchronised
+    the host."""
     world = dist.get_world_size(group)
     dev = ids.device
     cdev = _coll_device(group, dev)
@@ -786,4 +999,11 @@ def all_gather_results(ids: torch.Tensor, vals: torch.Tensor, group):
     got = [torch.empty_like(buf) for _ in range(world)]
     dist.all_gather(got, buf, group=group)
     rows = torch.cat([g[:s] for g, s in zip(got, sizes)]).to(dev)
+    if exact_ids:
+        mine = torch.zeros(m, dtype=torch.int64, device=cdev)
+        mine[:ids.numel()] = ids.to(cdev)
+        parts = [torch.empty_like(mine) for _ in range(world)]
+        dist.all_gather(parts, mine, group=group)
+        keys = torch.cat([p[:s] for p, s in zip(parts, sizes)]).to(dev)
+        return keys, rows[:, 1:].to(vals.dtype).contiguous()
     return rows[:, 0].round().to(torch.int64), rows[:, 1:].to(vals.dtype).contiguous()
