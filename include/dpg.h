@@ -527,6 +527,18 @@ int dpg_shard_records(dpg_ctx *ctx, const int64_t *pid, const int64_t *pk, const
  * Stream-ordered, no host synchronisation. */
 int dpg_check_shard(dpg_ctx *ctx, const int64_t *pid, int64_t n, int nranks, int rank,
                     int64_t *n_bad, void *stream);
+/* The same two calls for wide privacy ids (ColumnarData(wide_privacy_ids=True):
+ * any int64): identical contracts, arguments and errors; only the owner is
+ * another function, of all 64 bits of the id,
+ *   shard_wide(pid) = ((fmix64(pid) >> 32) * nranks) >> 32
+ * (fmix64 as given with the key dictionary below; host side:
+ * distributed.shard_of_wide = distributed.key_owner).  Ids that differ only
+ * above bit 31, which shard() sends to one rank, spread over all of them. */
+int dpg_shard_records_wide(dpg_ctx *ctx, const int64_t *pid, const int64_t *pk,
+                           const double *value, int64_t n, int nranks, int64_t *out_pid,
+                           int64_t *out_pk, double *out_value, int64_t *counts, void *stream);
+int dpg_check_shard_wide(dpg_ctx *ctx, const int64_t *pid, int64_t n, int nranks, int rank,
+                         int64_t *n_bad, void *stream);
 
 /* ---- multi-GPU: partition-keyed items to the rank that owns their partition ----
  * A release with percentiles or VECTOR_SUM sends its kept tree keys, or the
@@ -604,6 +616,25 @@ int dpg_keydict_assign(dpg_ctx *ctx, const int64_t *keys, const int64_t *ids, in
 int dpg_keydict_lookup(dpg_ctx *ctx, const int64_t *keys, int64_t n, const uint64_t *slots,
                        const uint32_t *slot_ids, int64_t capacity, int64_t *out_ids,
                        int64_t *n_missing, void *stream);
+/* Insert once, never probe again (wide privacy ids:
+ * distributed.encode_privacy_ids).  The table is write-once and a key never
+ * moves, so the slot a record finds when it is inserted is final.  The two
+ * calls below follow the contract of the four above.
+ *
+ * dpg_keydict_insert with the same protocol and the same info counters, which
+ * also stores every record's final slot: out_slots[i] (device uint32[n]) is
+ * the slot that holds keys[i], or 0xFFFFFFFF (never a slot: capacity <= 2^31)
+ * for a record that holds the reserved key or found no slot.  May be called
+ * several times on one table. */
+int dpg_keydict_insert_slots(dpg_ctx *ctx, const int64_t *keys, int64_t n, uint64_t *slots,
+                             int64_t capacity, uint32_t *out_slots, int64_t *info, void *stream);
+/* out_ids[i] (device int64[n]) = slot_ids[out_slots[i]] for i < n; an entry
+ * that is not a slot of the table (0xFFFFFFFF) gives -1 and *n_missing (device
+ * int64) += 1.  Reads neither the keys nor the slots: 4 bytes in, 8 bytes out
+ * and one 4-byte gather per record. */
+int dpg_keydict_gather_ids(dpg_ctx *ctx, const uint32_t *out_slots, int64_t n,
+                           const uint32_t *slot_ids, int64_t capacity, int64_t *out_ids,
+                           int64_t *n_missing, void *stream);
 
 /* ---- multi-GPU utility analysis: pairs to the rank that owns their partition ----
  * The per-partition utility combiners need every (privacy id, partition) pair

@@ -29,9 +29,11 @@ EXPORTED = ("dpg_ctx_create", "dpg_ctx_destroy", "dpg_last_error", "dpg_set_seed
             "dpg_vector_index", "dpg_vector_sums", "dpg_vector_clip_noise",
             "dpg_sample_partitions", "dpg_partition_summary",
             "dpg_keydict_insert", "dpg_keydict_keys", "dpg_keydict_assign",
-            "dpg_keydict_lookup")
+            "dpg_keydict_lookup", "dpg_keydict_insert_slots", "dpg_keydict_gather_ids",
+            "dpg_shard_records_wide", "dpg_check_shard_wide")
 
 KEYDICT_EMPTY = 1 << 63  # DPG_KEYDICT_EMPTY: the bit pattern of INT64_MIN, the reserved key
+KEYDICT_NO_SLOT = 0xFFFFFFFF  # dpg_keydict_insert_slots: a reserved or lost record
 
 COMM_ID_BYTES = 128  # DPG_COMM_ID_BYTES
 
@@ -284,6 +286,14 @@ def load():
         lib.dpg_keydict_assign.restype = ctypes.c_int
         lib.dpg_keydict_lookup.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, vp]
         lib.dpg_keydict_lookup.restype = ctypes.c_int
+        lib.dpg_keydict_insert_slots.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp]
+        lib.dpg_keydict_insert_slots.restype = ctypes.c_int
+        lib.dpg_keydict_gather_ids.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp]
+        lib.dpg_keydict_gather_ids.restype = ctypes.c_int
+        lib.dpg_shard_records_wide.argtypes = lib.dpg_shard_records.argtypes
+        lib.dpg_shard_records_wide.restype = ctypes.c_int
+        lib.dpg_check_shard_wide.argtypes = lib.dpg_check_shard.argtypes
+        lib.dpg_check_shard_wide.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -393,6 +403,21 @@ class Context:
         """Device int64 at n_bad_ptr = records whose owner is not `rank`."""
         st = self.lib.dpg_check_shard(self.handle, pid_ptr, n, nranks, rank, n_bad_ptr, stream)
         self.check(st, "dpg_check_shard")
+
+    def shard_records_wide(self, pid_ptr, pk_ptr, value_ptr, n, nranks, out_pid_ptr, out_pk_ptr,
+                           out_value_ptr, counts_ptr, stream):
+        """shard_records by distributed.shard_of_wide(pid, nranks): the owner
+        of a wide privacy id (ColumnarData(wide_privacy_ids=True))."""
+        st = self.lib.dpg_shard_records_wide(self.handle, pid_ptr, pk_ptr, value_ptr, n, nranks,
+                                             out_pid_ptr, out_pk_ptr, out_value_ptr, counts_ptr,
+                                             stream)
+        self.check(st, "dpg_shard_records_wide")
+
+    def check_shard_wide(self, pid_ptr, n, nranks, rank, n_bad_ptr, stream):
+        """check_shard by distributed.shard_of_wide."""
+        st = self.lib.dpg_check_shard_wide(self.handle, pid_ptr, n, nranks, rank, n_bad_ptr,
+                                           stream)
+        self.check(st, "dpg_check_shard_wide")
 
     def owner_split_keys(self, keys_ptr, n_keys_ptr, n_max, low_bits, nranks, out_keys_ptr,
                          out_src_ptr, counts_ptr, stream):
@@ -593,6 +618,23 @@ class Context:
         st = self.lib.dpg_keydict_lookup(self.handle, keys_ptr, int(n), slots_ptr, slot_ids_ptr,
                                          int(capacity), out_ids_ptr, n_missing_ptr, stream)
         self.check(st, "dpg_keydict_lookup")
+
+    def keydict_insert_slots(self, keys_ptr, n, slots_ptr, capacity, out_slots_ptr, info_ptr,
+                             stream):
+        """keydict_insert that also stores every record's final slot in
+        out_slots (device uint32[n]); KEYDICT_NO_SLOT for a record that holds
+        the reserved key or found no slot."""
+        st = self.lib.dpg_keydict_insert_slots(self.handle, keys_ptr, int(n), slots_ptr,
+                                               int(capacity), out_slots_ptr, info_ptr, stream)
+        self.check(st, "dpg_keydict_insert_slots")
+
+    def keydict_gather_ids(self, out_slots_ptr, n, slot_ids_ptr, capacity, out_ids_ptr,
+                           n_missing_ptr, stream):
+        """out_ids[i] (device int64) = slot_ids[out_slots[i]]; KEYDICT_NO_SLOT
+        gives -1, which the device int64 at n_missing_ptr counts."""
+        st = self.lib.dpg_keydict_gather_ids(self.handle, out_slots_ptr, int(n), slot_ids_ptr,
+                                             int(capacity), out_ids_ptr, n_missing_ptr, stream)
+        self.check(st, "dpg_keydict_gather_ids")
 
     def stage_times(self):
         names = ctypes.create_string_buffer(4096)

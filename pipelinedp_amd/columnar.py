@@ -15,6 +15,9 @@ dense partition ids in [0, P).  Integer keys that already satisfy this are
 used as they are; anything else (strings, tuples, ints spread wider) is
 dictionary-encoded (`unique` + inverse), and the partition dictionary maps
 results back.  Encoding is ingest, not part of the DP computation.
+ColumnarData(wide_privacy_ids=True) leaves int64 privacy ids of any span as
+they are; the device numbers them after the records are placed
+(distributed.encode_privacy_ids).
 """
 import dataclasses
 from collections.abc import Mapping
@@ -60,7 +63,24 @@ class ColumnarData:
     Results carry the caller's keys.  `max_distinct_partition_keys`: an upper
     bound on one rank's distinct partition keys, public ones included, which
     sizes the hash table (else the record count does); a bound that is too
-    small raises ValueError on every rank."""
+    small raises ValueError on every rank.
+
+    `wide_privacy_ids` (opt-in): `pid` holds any int64 values but INT64_MIN --
+    hashed user ids, half a UUID, tenant << 32 | user -- however wide they
+    span.  The device gives them dense ids in a rank-local hash dictionary
+    (distributed.encode_privacy_ids): the id of a
+    privacy id is its ascending rank among the rank's distinct ids, which is
+    what the default encoding of one process gives, without its sorts of the
+    record column.  It works with and without `n_partitions`, with
+    `sparse_partition_keys` and under every `sharding` mode; the owner of a
+    privacy id is then distributed.shard_of_wide(pid, R), a hash of all 64
+    bits, so a caller who pre-shards for "trusted" uses that.  `pid` must be an
+    integer tensor or array (TypeError otherwise) and `privacy_id_range` must
+    not be given.  `max_distinct_privacy_ids`: an upper bound on one rank's
+    distinct privacy ids, which sizes the hash table (else the record count
+    does); a bound that is too small raises ValueError on every rank.  With
+    contribution_bounds_already_enforced the privacy ids are not read and the
+    flag does nothing."""
     pid: Any = None
     pk: Any = None
     value: Any = None
@@ -70,6 +90,8 @@ class ColumnarData:
     sharding: str = "trusted"
     sparse_partition_keys: bool = False
     max_distinct_partition_keys: Optional[int] = None
+    wide_privacy_ids: bool = False
+    max_distinct_privacy_ids: Optional[int] = None
 
     def __post_init__(self):
         if self.sharding not in SHARDING_MODES:
@@ -77,6 +99,12 @@ class ColumnarData:
         if self.sparse_partition_keys and self.n_partitions is not None:
             raise ValueError("sparse_partition_keys=True builds the dense partition ids itself: "
                              "n_partitions must not be given")
+        if self.wide_privacy_ids:
+            if self.privacy_id_range is not None:
+                raise ValueError("wide_privacy_ids=True encodes the privacy ids itself: "
+                                 "privacy_id_range must not be given")
+            if self.pid is not None:
+                _check_wide_pid(self.pid)
 
     def __getitem__(self, name):
         return getattr(self, name)
@@ -111,6 +139,11 @@ class EncodedInput:
     # replaces them by global dense ids
     pk_sparse: bool = False
     public_keys: Optional[torch.Tensor] = None
+    # wide_privacy_ids: pid still holds the caller's int64 values (pid_min =
+    # pid_count = 0) until distributed.encode_privacy_ids replaces them by the
+    # rank's dense ids; max_distinct_pids sizes its table
+    pid_wide: bool = False
+    max_distinct_pids: Optional[int] = None
 
 
 def _extract(col, extractor):
@@ -136,6 +169,12 @@ def _integer_like(x) -> bool:
     if isinstance(x, torch.Tensor):
         return not x.is_floating_point() and not x.is_complex() and x.dtype != torch.bool
     return np.asarray(x).dtype.kind in "iu"
+
+
+def _check_wide_pid(pid) -> None:
+    if not (isinstance(pid, (torch.Tensor, np.ndarray)) and _integer_like(pid)):
+        raise TypeError("wide_privacy_ids=True needs integers: an integer tensor or array of "
+                        "privacy ids")
 
 
 def _is_int_key(k) -> bool:
@@ -353,10 +392,21 @@ def encode(col, extractors, device: torch.device, need_values: bool,
     pid_ids = None
     pid_min, pid_count = 0, 0
     pid_unencoded = False
+    # ColumnarData(wide_privacy_ids=True): the ids stay as they are and
+    # distributed.encode_privacy_ids builds the rank's dictionary once the
+    # records are placed
+    wide = need_pid and isinstance(col, ColumnarData) and col.wide_privacy_ids
     if need_pid:
         if pid is None:
             raise ValueError("privacy_id_extractor must be set")
-        if _integer_like(pid):
+        if wide:
+            if pid_range is not None:
+                raise ValueError("wide_privacy_ids=True encodes the privacy ids itself: "
+                                 "privacy_id_range must not be given")
+            _check_wide_pid(pid)
+            pid_ids = _to_tensor(pid, device).to(torch.int64)
+            pid_unencoded = True
+        elif _integer_like(pid):
             pid_t = _to_tensor(pid, device).to(torch.int64)
             pid_unencoded = True
             if pid_range is not None:
@@ -387,7 +437,8 @@ def encode(col, extractors, device: torch.device, need_values: bool,
                        partitions_declared=hint is not None and key_table is None,
                        pid_unencoded=pid_unencoded,
                        pid_range_declared=pid_unencoded and pid_range is not None,
-                       pk_sparse=bool(sparse), public_keys=sparse_public)
+                       pk_sparse=bool(sparse), public_keys=sparse_public, pid_wide=bool(wide),
+                       max_distinct_pids=col.max_distinct_privacy_ids if wide else None)
     if pub_range is not None:
         enc.public_mask, enc.public_count = _range_bitmap(*pub_range, int(P), device)
     elif pub_dense is not None:

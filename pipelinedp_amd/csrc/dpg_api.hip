@@ -2917,9 +2917,14 @@ int dpg_import_error(dpg_ctx *ctx, const double *src, int64_t n, void *stream) {
     return st;
 }
 
-int dpg_shard_records(dpg_ctx *ctx, const int64_t *pid, const int64_t *pk, const double *value,
-                      int64_t n, int nranks, int64_t *out_pid, int64_t *out_pk,
-                      double *out_value, int64_t *counts, void *stream) {
+// dpg_shard_records / dpg_check_shard and their _wide forms: one body, the
+// destination function (dpg_shard.h ShardLow32 / ShardWide) a template parameter
+extern "C++" {
+namespace {
+template <class Dest>
+int shard_records_impl(dpg_ctx *ctx, const int64_t *pid, const int64_t *pk, const double *value,
+                       int64_t n, int nranks, int64_t *out_pid, int64_t *out_pk,
+                       double *out_value, int64_t *counts, void *stream) {
     if (!ctx) return DPG_ERR_INVALID_ARG;
     if (nranks < 1 || nranks > DPG_SHARD_MAX_RANKS)
         return fail(ctx, DPG_ERR_INVALID_ARG, "nranks must be in [1, DPG_SHARD_MAX_RANKS]");
@@ -2945,7 +2950,7 @@ int dpg_shard_records(dpg_ctx *ctx, const int64_t *pid, const int64_t *pk, const
     const uint32_t nchunks = (M + kScanChunk - 1) / kScanChunk;
     WS(tiles, uint32_t, "shard.tiles", M);
     WS(sums, uint32_t, "shard.sums", nchunks);
-    k_shard_count<<<ntiles, kShThreads, 0, s>>>(pid, (uint32_t)n, R, bits, ntiles, tiles);
+    k_shard_count<Dest><<<ntiles, kShThreads, 0, s>>>(pid, (uint32_t)n, R, bits, ntiles, tiles);
     LAUNCH_CHECK();
     k_shard_scan_sums<<<nchunks, kShThreads, 0, s>>>(tiles, M, sums);
     LAUNCH_CHECK();
@@ -2958,19 +2963,18 @@ int dpg_shard_records(dpg_ctx *ctx, const int64_t *pid, const int64_t *pk, const
     // A/B switch: DPG_SHARD_STAGE=0 stores straight from registers
     const char *e = std::getenv("DPG_SHARD_STAGE");
     if (e ? std::atoi(e) != 0 : true)
-        k_shard_scatter<true><<<ntiles, kShThreads, 0, s>>>(pid, pk, value, (uint32_t)n, R, bits,
-                                                            ntiles, tiles, out_pid, out_pk,
-                                                            out_value);
+        k_shard_scatter<true, Dest><<<ntiles, kShThreads, 0, s>>>(
+            pid, pk, value, (uint32_t)n, R, bits, ntiles, tiles, out_pid, out_pk, out_value);
     else
-        k_shard_scatter<false><<<ntiles, kShThreads, 0, s>>>(pid, pk, value, (uint32_t)n, R, bits,
-                                                             ntiles, tiles, out_pid, out_pk,
-                                                             out_value);
+        k_shard_scatter<false, Dest><<<ntiles, kShThreads, 0, s>>>(
+            pid, pk, value, (uint32_t)n, R, bits, ntiles, tiles, out_pid, out_pk, out_value);
     LAUNCH_CHECK();
     return st;
 }
 
-int dpg_check_shard(dpg_ctx *ctx, const int64_t *pid, int64_t n, int nranks, int rank,
-                    int64_t *n_bad, void *stream) {
+template <class Dest>
+int check_shard_impl(dpg_ctx *ctx, const int64_t *pid, int64_t n, int nranks, int rank,
+                     int64_t *n_bad, void *stream) {
     if (!ctx) return DPG_ERR_INVALID_ARG;
     if (nranks < 1 || nranks > DPG_SHARD_MAX_RANKS || rank < 0 || rank >= nranks)
         return fail(ctx, DPG_ERR_INVALID_ARG, "nranks must be in [1, DPG_SHARD_MAX_RANKS], rank in [0, nranks)");
@@ -2983,11 +2987,37 @@ int dpg_check_shard(dpg_ctx *ctx, const int64_t *pid, int64_t n, int nranks, int
     if (n > 0) {
         const unsigned blocks = (unsigned)std::min<int64_t>((n + kShThreads - 1) / kShThreads,
                                                             (int64_t)ctx->n_cu * 8);
-        k_check_shard<<<blocks, kShThreads, 0, s>>>(pid, n, (uint32_t)nranks, (uint32_t)rank,
-                                                    reinterpret_cast<unsigned long long *>(n_bad));
+        k_check_shard<Dest><<<blocks, kShThreads, 0, s>>>(
+            pid, n, (uint32_t)nranks, (uint32_t)rank, reinterpret_cast<unsigned long long *>(n_bad));
         LAUNCH_CHECK();
     }
     return st;
+}
+}  // namespace
+}  // extern "C++"
+
+int dpg_shard_records(dpg_ctx *ctx, const int64_t *pid, const int64_t *pk, const double *value,
+                      int64_t n, int nranks, int64_t *out_pid, int64_t *out_pk,
+                      double *out_value, int64_t *counts, void *stream) {
+    return shard_records_impl<ShardLow32>(ctx, pid, pk, value, n, nranks, out_pid, out_pk,
+                                          out_value, counts, stream);
+}
+
+int dpg_shard_records_wide(dpg_ctx *ctx, const int64_t *pid, const int64_t *pk,
+                           const double *value, int64_t n, int nranks, int64_t *out_pid,
+                           int64_t *out_pk, double *out_value, int64_t *counts, void *stream) {
+    return shard_records_impl<ShardWide>(ctx, pid, pk, value, n, nranks, out_pid, out_pk,
+                                         out_value, counts, stream);
+}
+
+int dpg_check_shard(dpg_ctx *ctx, const int64_t *pid, int64_t n, int nranks, int rank,
+                    int64_t *n_bad, void *stream) {
+    return check_shard_impl<ShardLow32>(ctx, pid, n, nranks, rank, n_bad, stream);
+}
+
+int dpg_check_shard_wide(dpg_ctx *ctx, const int64_t *pid, int64_t n, int nranks, int rank,
+                         int64_t *n_bad, void *stream) {
+    return check_shard_impl<ShardWide>(ctx, pid, n, nranks, rank, n_bad, stream);
 }
 
 int dpg_owner_split_keys(dpg_ctx *ctx, const uint64_t *keys, const int64_t *n_keys, int64_t n_max,
@@ -3122,6 +3152,45 @@ int dpg_keydict_lookup(dpg_ctx *ctx, const int64_t *keys, int64_t n, const uint6
     k_keydict_lookup<<<keydict_blocks(ctx, n), kKdThreads, 0, s>>>(
         reinterpret_cast<const uint64_t *>(keys), (uint32_t)n, slots, slot_ids,
         (uint32_t)(capacity - 1), out_ids, reinterpret_cast<unsigned long long *>(n_missing));
+    LAUNCH_CHECK();
+    return DPG_OK;
+}
+
+int dpg_keydict_insert_slots(dpg_ctx *ctx, const int64_t *keys, int64_t n, uint64_t *slots,
+                             int64_t capacity, uint32_t *out_slots, int64_t *info, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (const char *e = keydict_table_error(slots, capacity)) return fail(ctx, DPG_ERR_INVALID_ARG, e);
+    if (n < 0 || !info || (n > 0 && (!keys || !out_slots)))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "n < 0, or keys, out_slots or info is NULL");
+    if (n >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n must be < 2^31 per device");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) return DPG_OK;
+    k_keydict_insert_slots<<<keydict_blocks(ctx, n), kKdThreads, 0, s>>>(
+        reinterpret_cast<const uint64_t *>(keys), (uint32_t)n, slots, (uint32_t)(capacity - 1),
+        out_slots, reinterpret_cast<unsigned long long *>(info));
+    LAUNCH_CHECK();
+    return DPG_OK;
+}
+
+int dpg_keydict_gather_ids(dpg_ctx *ctx, const uint32_t *out_slots, int64_t n,
+                           const uint32_t *slot_ids, int64_t capacity, int64_t *out_ids,
+                           int64_t *n_missing, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (!slot_ids) return fail(ctx, DPG_ERR_INVALID_ARG, "slot_ids is NULL");
+    if (const char *e = keydict_table_error(slot_ids, capacity)) return fail(ctx, DPG_ERR_INVALID_ARG, e);
+    if (n < 0 || !n_missing || (n > 0 && (!out_slots || !out_ids)))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "n < 0, or out_slots, out_ids or n_missing is NULL");
+    if (n >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n must be < 2^31 per device");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) return DPG_OK;
+    const int64_t per_block = (int64_t)kKdThreads * kKdGather;
+    const unsigned blocks = (unsigned)std::min<int64_t>((n + per_block - 1) / per_block,
+                                                        (int64_t)ctx->n_cu * 8);
+    k_keydict_gather_ids<<<blocks, kKdThreads, 0, s>>>(
+        out_slots, (uint32_t)n, slot_ids, (uint32_t)(capacity - 1), out_ids,
+        reinterpret_cast<unsigned long long *>(n_missing));
     LAUNCH_CHECK();
     return DPG_OK;
 }

@@ -244,6 +244,18 @@ __host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
     return h;
 }
 
+// Murmur3's 64-bit finaliser: the hash of the key dictionary (dpg_keydict.h)
+// and of the 64-bit shard function (dpg_shard.h); host side:
+// distributed.key_hash.
+__host__ __device__ __forceinline__ uint64_t fmix64(uint64_t k) {
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ull;
+    k ^= k >> 33;
+    return k;
+}
+
 // Sampling priorities (DESIGN.md "Randomness"): keyed chains of the murmur3
 // finalizer.  Sampling only has to be uniform without replacement -- the
 // privacy guarantee holds for any choice of kept records -- so a cheap mixer

@@ -25,6 +25,11 @@
 // INT64_MIN has the bit pattern of kKdEmpty: it is reserved, counted and never
 // stored.
 //
+// Wide privacy ids (distributed.encode_privacy_ids) use the same table
+// rank-locally and probe it once: dpg_keydict_insert_slots remembers the slot
+// every record found -- final, since a key never moves -- and
+// dpg_keydict_gather_ids reads slot_ids there.
+//
 // Every probe loop runs at most `capacity` steps, so a full table ends the
 // call (insert counts the record in info[1]); nothing spins.  The other three
 // kernels run behind the inserts in stream order and only read the slots.
@@ -36,15 +41,7 @@ namespace dpg {
 
 constexpr uint64_t kKdEmpty = 0x8000000000000000ull;
 constexpr uint32_t kKdThreads = 256;
-
-__host__ __device__ __forceinline__ uint64_t fmix64(uint64_t k) {
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return k;
-}
+constexpr uint32_t kKdNoSlot = 0xFFFFFFFFu;  // capacity <= 2^31: never a slot
 
 // Adds the wave's sum of x to *dst with one atomic (all lanes active).
 __device__ __forceinline__ void kd_wave_add(unsigned long long *dst, uint32_t x) {
@@ -96,6 +93,71 @@ __global__ __launch_bounds__(kKdThreads) void k_keydict_insert(const uint64_t *k
     }
     kd_wave_add(info, reserved);
     kd_wave_add(info + 1, lost);
+}
+
+// k_keydict_insert that also remembers where every record ended up.  A slot is
+// write-once and a key never moves, so the slot a record finds here is final:
+// out_slots[i] stands for the key from now on, and k_keydict_gather_ids turns
+// it into an id without reading the key column or walking a chain again.  A
+// reserved or lost record stores kKdNoSlot.
+__global__ __launch_bounds__(kKdThreads) void k_keydict_insert_slots(
+    const uint64_t *keys, uint32_t n, uint64_t *slots, uint32_t mask, uint32_t *out_slots,
+    unsigned long long *info) {
+    uint32_t reserved = 0, lost = 0;
+    const uint32_t stride = gridDim.x * kKdThreads;
+    // i stays below n + stride < 2^32: n < 2^31 and the grid has fewer threads
+    for (uint32_t i = blockIdx.x * kKdThreads + threadIdx.x; i < n; i += stride) {
+        const uint64_t key = keys[i];
+        if (key == kKdEmpty) {
+            ++reserved;
+            out_slots[i] = kKdNoSlot;
+            continue;
+        }
+        uint32_t s = (uint32_t)fmix64(key) & mask;
+        bool placed = false;
+        for (uint32_t step = 0; step <= mask; ++step) {
+            uint64_t cur = slots[s];
+            if (cur == kKdEmpty)
+                cur = atomicCAS(reinterpret_cast<unsigned long long *>(slots + s),
+                                (unsigned long long)kKdEmpty, (unsigned long long)key);
+            if (cur == key || cur == kKdEmpty) {
+                placed = true;
+                break;
+            }
+            s = (s + 1u) & mask;
+        }
+        out_slots[i] = placed ? s : kKdNoSlot;
+        lost += placed ? 0u : 1u;
+    }
+    kd_wave_add(info, reserved);
+    kd_wave_add(info + 1, lost);
+}
+
+// out_ids[i] = slot_ids[out_slots[i]]: 4 bytes in, 8 out and one 4-byte gather
+// per record.  Four records per lane and trip, their gathers in flight
+// together; anything that is not a slot (kKdNoSlot) gives -1 and is counted.
+constexpr uint32_t kKdGather = 4;
+__global__ __launch_bounds__(kKdThreads) void k_keydict_gather_ids(
+    const uint32_t *out_slots, uint32_t n, const uint32_t *slot_ids, uint32_t mask,
+    int64_t *out_ids, unsigned long long *n_missing) {
+    uint32_t missing = 0;
+    const uint32_t stride = gridDim.x * kKdThreads;
+    // i0 + 3 * stride stays below n + 7 * stride < 2^32: n < 2^31, stride < 2^27
+    for (uint32_t i0 = blockIdx.x * kKdThreads + threadIdx.x; i0 < n; i0 += kKdGather * stride) {
+        uint32_t s[kKdGather], id[kKdGather];
+#pragma unroll
+        for (uint32_t k = 0; k < kKdGather; ++k)
+            s[k] = i0 + k * stride < n ? out_slots[i0 + k * stride] : kKdNoSlot;
+#pragma unroll
+        for (uint32_t k = 0; k < kKdGather; ++k) id[k] = s[k] <= mask ? slot_ids[s[k]] : 0u;
+#pragma unroll
+        for (uint32_t k = 0; k < kKdGather; ++k) {
+            if (i0 + k * stride >= n) continue;
+            out_ids[i0 + k * stride] = s[k] <= mask ? (int64_t)id[k] : -1;
+            missing += s[k] <= mask ? 0u : 1u;
+        }
+    }
+    kd_wave_add(n_missing, missing);
 }
 
 // Compaction of the occupied slots: a wave reserves one run of out_keys for

@@ -3,8 +3,10 @@
 // dpg_shard_records orders the records of one rank destination-major before
 // the record all-to-all of a multi-GPU release (distributed.shuffle_records):
 // destination d = shard(pid) = umulhi((uint32)pid * 0x9E3779B1, R), the
-// device form of distributed.shard_of, and the records of one destination
-// keep their input order.
+// device form of distributed.shard_of -- or, for wide privacy ids
+// (dpg_shard_records_wide), ((fmix64(pid) >> 32) * R) >> 32, the device form
+// of distributed.shard_of_wide -- and the records of one destination keep
+// their input order.
 //
 // Three stream-ordered steps, nothing through the host:
 //   count    one workgroup per tile of DPG_SHARD_TILE records reads pid only
@@ -48,6 +50,25 @@ __device__ __forceinline__ uint32_t shard_dest(int64_t pid, uint32_t R) {
     return __umulhi((uint32_t)pid * 0x9E3779B1u, R);
 }
 
+// The destination function is a template parameter of the kernels below.
+// ShardLow32 is shard_dest, the owner of privacy ids that span at most 2^32
+// values (dpg_shard_records, dpg_check_shard).  ShardWide hashes all 64 bits:
+// the high half of fmix64, as the key dictionary's owner
+// (distributed.shard_of_wide = distributed.key_owner), for
+// ColumnarData(wide_privacy_ids=True) (dpg_shard_records_wide,
+// dpg_check_shard_wide) -- ids that differ only above bit 31 spread over the
+// ranks instead of meeting on one.
+struct ShardLow32 {
+    static __device__ __forceinline__ uint32_t of(int64_t pid, uint32_t R) {
+        return shard_dest(pid, R);
+    }
+};
+struct ShardWide {
+    static __device__ __forceinline__ uint32_t of(int64_t pid, uint32_t R) {
+        return (uint32_t)(((fmix64((uint64_t)pid) >> 32) * R) >> 32);
+    }
+};
+
 // One step of a wave: the position of this lane's record among the wave's
 // records of destination d so far; cnt (the wave's own LDS row) advances by
 // the step's records.  Every lane of the wave calls it; lanes past the end of
@@ -68,6 +89,7 @@ __device__ __forceinline__ uint32_t shard_step(uint32_t *cnt, uint32_t d, bool v
     return before + rank;
 }
 
+template <class Dest>
 __global__ __launch_bounds__(kShThreads) void k_shard_count(const int64_t *pid, uint32_t n,
                                                             uint32_t R, uint32_t bits,
                                                             uint32_t ntiles, uint32_t *tcnt) {
@@ -83,7 +105,7 @@ __global__ __launch_bounds__(kShThreads) void k_shard_count(const int64_t *pid, 
 #pragma unroll
     for (uint32_t k = 0; k < kShSteps; ++k) {
         const bool valid = i0 + 64u * k < n;
-        shard_step(wcnt[w], valid ? shard_dest(p[k], R) : 0u, valid, bits);
+        shard_step(wcnt[w], valid ? Dest::of(p[k], R) : 0u, valid, bits);
     }
     __syncthreads();
     if (tid < R) {
@@ -94,7 +116,7 @@ __global__ __launch_bounds__(kShThreads) void k_shard_count(const int64_t *pid, 
     }
 }
 
-template <bool kStage>
+template <bool kStage, class Dest>
 __global__ __launch_bounds__(kShThreads) void k_shard_scatter(
     const int64_t *pid, const int64_t *pk, const double *value, uint32_t n, uint32_t R,
     uint32_t bits, uint32_t ntiles, const uint32_t *tbase, int64_t *out_pid, int64_t *out_pk,
@@ -123,7 +145,7 @@ __global__ __launch_bounds__(kShThreads) void k_shard_scatter(
 #pragma unroll
     for (uint32_t k = 0; k < kShSteps; ++k) {
         const bool valid = i0 + 64u * k < n;
-        d[k] = valid ? shard_dest(p[k], R) : 0u;
+        d[k] = valid ? Dest::of(p[k], R) : 0u;
         g[k] = shard_step(wcnt[w], d[k], valid, bits);
     }
     __syncthreads();
@@ -263,13 +285,14 @@ __global__ void k_shard_totals(const uint32_t *tbase, uint32_t n, uint32_t R, ui
 }
 
 // *n_bad += records whose destination is not `rank` (zeroed by the caller).
+template <class Dest>
 __global__ __launch_bounds__(kShThreads) void k_check_shard(const int64_t *pid, int64_t n,
                                                             uint32_t R, uint32_t rank,
                                                             unsigned long long *n_bad) {
     uint32_t bad = 0;
     for (int64_t i = (int64_t)blockIdx.x * kShThreads + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * kShThreads)
-        bad += shard_dest(pid[i], R) != rank ? 1u : 0u;
+        bad += Dest::of(pid[i], R) != rank ? 1u : 0u;
     uint32_t total;
     wave_excl_scan(bad, total);
     if ((threadIdx.x & 63u) == 0 && total) atomicAdd(n_bad, (unsigned long long)total);

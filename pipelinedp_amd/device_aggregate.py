@@ -378,6 +378,8 @@ class DeviceAggregation:
                     f"VECTOR_SUM with vector_size={vector} needs ({enc.n}, {vector})")
             enc.value = enc.value.to(torch.float64).contiguous()
         self._place_records(enc)
+        # wide_privacy_ids: this rank's records get their dense privacy ids
+        distributed.encode_privacy_ids(enc, backend)
         bfields = self._bound_fields(P)
         l0 = (bfields["max_contributions"] if bfields["mode"] == combiners.MODE_PER_PID
               else bfields["max_partitions_contributed"])

@@ -92,6 +92,13 @@ id % R is that owner, and maps every record through the table (DESIGN.md
 section 16).  The kept results then carry the caller's keys
 (`all_gather_results(exact_ids=True)`).
 
+Privacy ids that span more than 2^32 values (ColumnarData(wide_privacy_ids=
+True): any int64 but INT64_MIN) are owned by `shard_of_wide`, a hash of all 64
+bits, in all three sharding modes, and get dense ids rank by rank once the
+records are in place: `encode_privacy_ids` numbers each rank's distinct ids in
+the same kind of hash table, probed once per record, and adds one all_reduce
+that makes every rank raise the same error.
+
 Every random draw is keyed by (stream seed, pid, pk) or (stream seed, pk)
 with global partition ids -- never by rank -- and the release nonce comes
 from rank 0, so the selected-partition set is identical for any world size
@@ -115,6 +122,15 @@ def shard_of(pid: torch.Tensor, world_size: int) -> torch.Tensor:
     bits the kernels bucket by)."""
     h = (pid.to(torch.int64) * 0x9E3779B1) & 0xFFFFFFFF
     return ((h * world_size) >> 32).to(torch.int64)
+
+
+def shard_of_wide(pid, world_size: int) -> torch.Tensor:
+    """Rank owning each wide privacy id (ColumnarData(wide_privacy_ids=True)):
+    `key_owner`, ((fmix64(pid) >> 32) * R) >> 32 -- a hash of all 64 bits, where
+    `shard_of` reads the low 32 only and sends ids that differ above them
+    (user << 32) to one rank.  Device form: dpg_shard_records_wide,
+    dpg_check_shard_wide."""
+    return key_owner(pid, world_size)
 
 
 def owned(P: int, world_size: int, rank: int) -> Tuple[int, int, int]:
@@ -194,8 +210,9 @@ def _split_sizes(counts: torch.Tensor, group, dev, what: str, items: str):
 
 
 def shuffle_records(pid: torch.Tensor, pk: torch.Tensor, value: Optional[torch.Tensor], group,
-                    ctx=None, stream=None):
-    """Delivers every record to the rank `shard_of(pid, R)`; returns this
+                    ctx=None, stream=None, wide: bool = False):
+    """Delivers every record to the rank `shard_of(pid, R)` -- wide=True (wide
+    privacy ids): `shard_of_wide(pid, R)`, dpg_shard_records_wide; returns this
     rank's (pid, pk, value) in source-rank order, input order within a source
     (value None stays None: every rank must pass None or none of them; a
     [n, D] value -- VECTOR_SUM rows, D the same on every rank -- travels row
@@ -228,17 +245,16 @@ def shuffle_records(pid: torch.Tensor, pk: torch.Tensor, value: Optional[torch.T
         col = torch.arange(n, dtype=torch.float64, device=dev) if rows else value
         s_val = torch.empty_like(col) if col is not None else None
         counts = torch.empty(world, dtype=torch.int64, device=dev)
-        ctx.shard_records(pid.data_ptr(), pk.data_ptr(),
-                          col.data_ptr() if col is not None else None, n, world,
-                          s_pid.data_ptr(), s_pk.data_ptr(),
-                          s_val.data_ptr() if s_val is not None else None,
-                          counts.data_ptr(), stream)
+        split = ctx.shard_records_wide if wide else ctx.shard_records
+        split(pid.data_ptr(), pk.data_ptr(), col.data_ptr() if col is not None else None, n,
+              world, s_pid.data_ptr(), s_pk.data_ptr(),
+              s_val.data_ptr() if s_val is not None else None, counts.data_ptr(), stream)
         if rows:
             s_val = value.index_select(0, s_val.to(torch.int64))
         del col
         counts = counts.cpu()  # the one host synchronisation
     else:
-        dest = shard_of(pid, world)
+        dest = shard_of_wide(pid, world) if wide else shard_of(pid, world)
         order = torch.argsort(dest, stable=True)
         counts = torch.bincount(dest, minlength=world).cpu()
         s_pid, s_pk = pid[order], pk[order]
@@ -541,7 +557,8 @@ def place_records(enc, backend, mode: str) -> None:
     nothing, 'verify' checks that this rank owns every privacy id it holds
     (one kernel, one all_reduce; every rank raises when any rank fails),
     'shuffle' sends every record to its owner (shuffle_records) and leaves
-    what arrives, with record id offset 0."""
+    what arrives, with record id offset 0.  Wide privacy ids (enc.pid_wide)
+    are owned by `shard_of_wide`: the check and the split are the _wide calls."""
     if backend.world_size <= 1 or mode == "trusted":
         return
     if not enc.pid_unencoded:
@@ -554,22 +571,169 @@ def place_records(enc, backend, mode: str) -> None:
         sptr = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         if mode == "verify":
             n_bad = torch.empty(1, dtype=torch.int64, device=dev)
-            backend.ctx.check_shard(ctypes.c_void_p(enc.pid.data_ptr()), enc.n,
-                                    backend.world_size, dist.get_rank(group), n_bad.data_ptr(),
-                                    sptr)
+            check = backend.ctx.check_shard_wide if enc.pid_wide else backend.ctx.check_shard
+            check(ctypes.c_void_p(enc.pid.data_ptr()), enc.n, backend.world_size,
+                  dist.get_rank(group), n_bad.data_ptr(), sptr)
             # no rank raises before the collective
             total = sum_over_ranks(n_bad, group)
             if total:
                 raise ValueError(
                     f"sharding='verify': {total} records are on a rank that does not own "
-                    f"their privacy id (distributed.shard_of); use sharding='shuffle'")
+                    f"their privacy id (distributed."
+                    f"{'shard_of_wide' if enc.pid_wide else 'shard_of'}); use sharding='shuffle'")
             return
         enc.pid, enc.pk, enc.value = shuffle_records(enc.pid, enc.pk, enc.value, group,
-                                                     backend.ctx, sptr)
+                                                     backend.ctx, sptr, wide=enc.pid_wide)
     enc.n = int(enc.pk.numel())
     enc.rec_id_offset = 0
     if not enc.pid_range_declared:  # a declared range is global; else the device reduces it
         enc.pid_min, enc.pid_count = 0, 0
+
+
+PID_DICT_ROUTES = ("slots", "lookup")
+# The product route of `local_pid_dictionary`, chosen by the A/B of DESIGN.md
+# section 17 (tools/bench_privacy_id_dictionary.py).
+PID_DICT_ROUTE = "slots"
+
+
+def _pid_capacity(n: int, max_distinct: Optional[int]) -> int:
+    """Slots of the privacy-id table: the power of two >= 2 x min(n,
+    max_distinct), in [64, 2^31] (the table calls' limit)."""
+    bound = n if max_distinct is None else min(n, max(0, int(max_distinct)))
+    return min(1 << 31, max(64, 1 << max(2 * bound - 1, 0).bit_length()))
+
+
+def local_pid_dictionary(pid: torch.Tensor, ctx, stream, max_distinct: Optional[int] = None,
+                         route: Optional[str] = None):
+    """The device half of `encode_privacy_ids` up to the error check: returns
+    (finish, D, n_reserved, n_lost) -- D distinct ids, the records holding the
+    reserved id and the records that found no slot, read back together (the
+    one host synchronisation) -- and `finish()`, which maps every record and
+    returns the int64 ids: the ascending rank of each record's id among the D.
+
+    route "slots": dpg_keydict_insert_slots remembers every record's slot and
+    dpg_keydict_gather_ids reads the id there -- the table is probed once per
+    record.  route "lookup": the composition of dpg_keydict_insert and
+    dpg_keydict_lookup that `build_key_dictionary` uses, which probes twice.
+    Both give the same ids; None takes PID_DICT_ROUTE."""
+    route = PID_DICT_ROUTE if route is None else route
+    if route not in PID_DICT_ROUTES:
+        raise ValueError(f"unknown privacy-id dictionary route {route!r}")
+    dev = pid.device
+    n = pid.numel()
+    capacity = _pid_capacity(n, max_distinct)
+    slots = torch.full((capacity,), _I64_MIN, dtype=torch.int64, device=dev)
+    info = torch.zeros(2, dtype=torch.int64, device=dev)
+    rec_slots = None
+    if route == "slots":
+        rec_slots = torch.empty(n, dtype=torch.int32, device=dev)  # uint32 bit patterns
+        ctx.keydict_insert_slots(pid.data_ptr(), n, slots.data_ptr(), capacity,
+                                 rec_slots.data_ptr(), info.data_ptr(), stream)
+    else:
+        ctx.keydict_insert(pid.data_ptr(), n, slots.data_ptr(), capacity, info.data_ptr(), stream)
+    found = torch.empty(capacity, dtype=torch.int64, device=dev)
+    n_found = torch.empty(1, dtype=torch.int64, device=dev)
+    ctx.keydict_keys(slots.data_ptr(), capacity, found.data_ptr(), n_found.data_ptr(), stream)
+    D, n_reserved, n_lost = torch.cat([n_found, info]).tolist()  # the one host synchronisation
+    biased = found[:D] ^ _I64_MIN  # unsigned order of id ^ 2^63 = signed order of id
+    distinct = torch.empty_like(biased)
+    ctx.sort_pairs_u64(biased.data_ptr(), None, D, 0, 64, distinct.data_ptr(), None, stream)
+    distinct ^= _I64_MIN
+    del found, biased
+    slot_ids = torch.empty(capacity, dtype=torch.int32, device=dev)
+    n_missing = torch.zeros(1, dtype=torch.int64, device=dev)
+    ranks = torch.arange(D, dtype=torch.int64, device=dev)
+    ctx.keydict_assign(distinct.data_ptr(), ranks.data_ptr(), D, slots.data_ptr(),
+                       slot_ids.data_ptr(), capacity, n_missing.data_ptr(), stream)
+
+    def finish() -> torch.Tensor:
+        # a record without an id is one that `info` counted, and the caller
+        # has raised for those: n_missing is not read back
+        ids = torch.empty(n, dtype=torch.int64, device=dev)
+        if route == "slots":
+            ctx.keydict_gather_ids(rec_slots.data_ptr(), n, slot_ids.data_ptr(), capacity,
+                                   ids.data_ptr(), n_missing.data_ptr(), stream)
+        else:
+            ctx.keydict_lookup(pid.data_ptr(), n, slots.data_ptr(), slot_ids.data_ptr(), capacity,
+                               ids.data_ptr(), n_missing.data_ptr(), stream)
+        return ids
+
+    return finish, D, n_reserved, n_lost
+
+
+def encode_privacy_ids(enc, backend) -> None:
+    """ColumnarData(wide_privacy_ids=True): replaces the caller's int64 privacy
+    ids in the encoded input `enc` (marked enc.pid_wide; else nothing happens)
+    by dense ids, in place, right after `place_records` -- under "shuffle" on
+    the received records.  Privacy ids never appear in a result and bounding
+    is shard-local, so the dictionary is rank-local: the id of a privacy id is
+    its ascending rank among this rank's distinct ids, exactly what
+    torch.unique(return_inverse=True) -- the default encoding of one process
+    -- gives.  No key travels.
+
+    Device tensors (the library context backend.ctx): `local_pid_dictionary`,
+    a write-once hash table of `_pid_capacity` slots (12 bytes per slot plus 8
+    for the compaction, and 4 bytes per record for the remembered slots) with
+    ONE host synchronisation, the read of the distinct count.  Host tensors
+    (the gloo CPU tests): torch.unique, the reserved count and the table's
+    capacity check mirrored.
+
+    Errors are agreed on before anyone raises.  With several ranks ONE
+    all_reduce (sum) carries each rank's records holding the reserved id
+    INT64_MIN, its records that found no slot and its other local
+    precondition failures (n >= 2^31, the table calls' limit); no rank raises
+    between `place_records` and this collective, a rank without records runs
+    it too, and after it every rank raises the same ValueError.  One process
+    raises directly."""
+    if not enc.pid_wide:
+        return
+    world = backend.world_size
+    group = backend.process_group if world > 1 else None
+    pid = enc.pid.to(torch.int64).contiguous().view(-1)
+    dev = pid.device
+    n = pid.numel()
+    max_distinct = enc.max_distinct_pids
+    too_many = int(n >= 1 << 31)
+    finish, D, n_reserved, n_lost = None, 0, 0, 0
+    if too_many:
+        pass
+    elif dev.type == "cuda":
+        with torch.cuda.device(dev):
+            sptr = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            finish, D, n_reserved, n_lost = local_pid_dictionary(pid, backend.ctx, sptr,
+                                                                 max_distinct)
+    else:
+        uniq, inv = torch.unique(pid, return_inverse=True)
+        n_reserved = int((pid == _I64_MIN).sum().item())
+        D = int(uniq.numel())
+        if max_distinct is not None:  # the device table's capacity, mirrored
+            n_lost = max(0, D - _pid_capacity(n, max_distinct))
+        finish = lambda: inv.to(torch.int64)
+    if world > 1:
+        t = torch.tensor([n_reserved, n_lost, too_many], dtype=torch.int64,
+                         device=_coll_device(group, dev))
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        n_reserved, n_lost, too_many = t.tolist()
+    if too_many:
+        raise ValueError("wide privacy ids: a rank holds 2^31 or more records; the id "
+                         "dictionary takes fewer")
+    if n_reserved:
+        raise ValueError(
+            f"wide privacy ids: {n_reserved} records hold the privacy id INT64_MIN (-2^63), "
+            f"which the id dictionary reserves")
+    if n_lost:
+        raise ValueError(
+            f"wide privacy ids: the id dictionary sized by max_distinct_privacy_ids="
+            f"{max_distinct} overflowed ({n_lost} records found no slot on their rank); raise "
+            f"max_distinct_privacy_ids to at least the number of distinct privacy ids of one "
+            f"rank")
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            enc.pid = finish()
+    else:
+        enc.pid = finish()
+    enc.pid_min, enc.pid_count = 0, max(1, D)
+    enc.pid_wide = False
 
 
 def exchange_owner_pairs(pairs: torch.Tensor, n_pairs: int, P: int, group, ctx=None,

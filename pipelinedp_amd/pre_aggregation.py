@@ -71,7 +71,9 @@ def device_pairs(col, extractors, backend, public_partitions, dev,
             raise ValueError(distributed.DENSE_IDS_ERROR)
         distributed.place_records(
             enc, backend, col.sharding if isinstance(col, columnar.ColumnarData) else "trusted")
-    bound = _native.BoundParams()
+    # wide_privacy_ids: this rank's records get their dense privacy ids
+    distributed.encode_privacy_ids(enc, backend)
+    bound =_native.BoundParams()
     bound.n_partitions = P
     bound.pid_min, bound.pid_count = enc.pid_min, enc.pid_count
     bound.rec_id_offset = enc.rec_id_offset
