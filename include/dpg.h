@@ -808,7 +808,11 @@ int dpg_vector_clip_noise(dpg_ctx *ctx, const double *sums, int64_t n_partitions
  * "partition2:scatter", "chunks", "bound.kernel=sort" (zero-length marker
  * of the small-chunk kernel that ran), "bound", "bound.wide" (sort kernel:
  * chunks of more than 256 candidates), "bound.medium", "bound.tail",
- * "items:hist", "items:scatter", "reduce". */
+ * "items:hist", "items:scatter", "reduce".  With DPG_DEBUG_ITEM_PATHS set
+ * in the environment (a test hook: one more host synchronisation) the
+ * zero-length markers "items.regions=window" / "items.regions=lookup" follow
+ * "items:scatter": sub-tiles of the first item level whose regions were
+ * resolved wave-uniformly / by the per-lane lookup. */
 int dpg_last_stage_times(dpg_ctx *ctx, char *names, size_t names_len,
                          double *ms, int32_t max_stages, int32_t *n_stages);
 

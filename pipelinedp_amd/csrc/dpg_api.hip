@@ -134,6 +134,9 @@ struct Control {  // device-side counters, zeroed per call
     uint32_t n_mchunks;  // single-bucket chunks above the small-chunk capacity
     uint32_t heavy_nfb;  // heavy buckets handed back to k_bound_big
     uint32_t pad_;
+    // sub-tiles of the first item level scattered with their regions resolved
+    // uniformly / by the per-lane lookup (SrcSeg; DPG_DEBUG_ITEM_PATHS)
+    uint32_t seg_paths[2];
     unsigned long long over_records;
     unsigned long long over2_records;
     unsigned long long pid_lo, pid_hi;  // order-preserving (x ^ 2^63) min / max
@@ -1211,6 +1214,15 @@ int bound_and_reduce(dpg_ctx *ctx, hipStream_t s, const Plan &pl, const R *recs,
 #define DPG_ITEM_IPT_WIDE 4  // 24-byte items per thread per sub-tile (LDS caps it at 5)
 #endif
     constexpr int kItemIpt = sizeof(Item) == 16 ? 8 : sizeof(Item) == 24 ? DPG_ITEM_IPT_WIDE : 4;
+#ifndef DPG_ITEM_IPT_SEG16
+    // 16-byte items per thread of the first item level (SrcSeg), which holds
+    // the regions' window beside the items: the largest count whose scatter
+    // keeps every register (8: 31 spilled, 6: 2, 5: none); same-box A/B of
+    // items:scatter, parent 0.89-0.90 ms: 8 -> 0.70, 6 -> 0.69, 5 -> 0.67-0.68
+    // (profiles/r9/)
+#define DPG_ITEM_IPT_SEG16 5
+#endif
+    constexpr int kSegIpt = sizeof(Item) == 16 ? DPG_ITEM_IPT_SEG16 : kItemIpt;
     // the items are partitioned by partition-key range: one level up to 1024
     // ranges, else two (pk >> (rbits + b2), then (pk >> rbits) mod 2^b2) --
     // the final segment index is the range id either way
@@ -1232,11 +1244,22 @@ int bound_and_reduce(dpg_ctx *ctx, hipStream_t s, const Plan &pl, const R *recs,
         const uint32_t b1 = rb - b2;
         const uint32_t F1 = nranges <= 1024 ? (uint32_t)std::max<int64_t>(1, nranges) : 1u << b1;
         WS(items2, Item, "items2", n_items);
-        const SrcSeg<Item> src1{items, wg_pre, wg_off, G + 1, kRB + b2};
-        int r = run_level<SrcSeg<Item>, Item, kItemIpt, 1024>(
+        // SrcSeg reads windows of kSegK regions (G >= the CUs of the device)
+        if (G + 1 < (uint32_t)kSegK) return fail(ctx, DPG_ERR_HIP, "internal: too few item regions");
+        const SrcSeg<Item> src1{items, wg_pre, wg_off, G + 1, kRB + b2, ctl->seg_paths};
+        int r = run_level<SrcSeg<Item>, Item, kSegIpt, 1024>(
             ctx, s, src1, 1u, nullptr, &ctl->item_cursor, nullptr, n_items, F1, b1, items2,
             "items", &baseR, &totR, &ctl->ntiles[4]);
         if (r) return r;
+        if (std::getenv("DPG_DEBUG_ITEM_PATHS")) {
+            // test hook: zero-length stage markers of the paths the item
+            // scatter's sub-tiles took (a host round trip)
+            uint32_t hp[2];
+            HIP_TRY(hipMemcpyAsync(hp, ctl->seg_paths, sizeof(hp), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (hp[0]) stage(ctx, s, "items.regions=window");
+            if (hp[1]) stage(ctx, s, "items.regions=lookup");
+        }
         sorted = items2;
         F = F1;
         if (b2 > 0) {

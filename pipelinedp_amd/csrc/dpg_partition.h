@@ -37,6 +37,8 @@ __host__ __device__ constexpr size_t a16(size_t x) { return (x + 15) & ~(size_t)
 typedef int64_t i64x2 __attribute__((ext_vector_type(2)));
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 typedef uint64_t u64x2a8 __attribute__((ext_vector_type(2), aligned(8)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 template <class Src, class = void>
 struct HasFetchPairs {
@@ -308,21 +310,214 @@ struct SrcAoS {
     }
 };
 
+// Sources read as a sequence of regions (SrcSeg): k_hist and k_scatter
+// resolve the regions of a whole sub-tile once, wave-uniformly (window()).
+template <class Src, class = void>
+struct HasRegions {
+    static constexpr bool value = false;
+};
+template <class Src>
+struct HasRegions<Src, decltype((void)Src::kRegions)> {
+    static constexpr bool value = Src::kRegions;
+};
+
+// Regions a sub-tile may straddle on the fast path of a region source.
+constexpr int kSegK = 8;
+
+// A pointer made provably uniform (scalar-load operands: sload_regions,
+// dpg_team.h sload_desc; a pointer the compiler keeps in vector registers is
+// not one).
+template <class T>
+__device__ __forceinline__ const T *uniform_ptr(const T *p) {
+    const uint64_t v = (uint64_t)(uintptr_t)p;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return reinterpret_cast<const T *>((uintptr_t)(((uint64_t)hi << 32) | lo));
+}
+
+// kSegK + 1 region boundaries and kSegK region offsets from two uniform
+// addresses into scalar registers, one round trip (loads only: nothing is
+// written through the scalar cache).  The outputs are early-clobber: the
+// loads are in flight while the later ones still read the addresses.
+struct SegBounds {  // scalars, not arrays: each stays in its scalar registers
+    int64_t p0, p1, p2, p3, p4, p5, p6, p7, p8;  // pre[lb + k]
+    int64_t o0, o1, o2, o3, o4, o5, o6, o7;      // off[lb + k]
+};
+__device__ __forceinline__ SegBounds sload_regions(const int64_t *pre, const int64_t *off) {
+    static_assert(kSegK == 8, "sload_regions lists its loads");
+    int64_t p0, p1, p2, p3, p4, p5, p6, p7, p8, o0, o1, o2, o3, o4, o5, o6, o7;
+    asm volatile(
+        "s_load_dwordx2 %0, %17, 0x0\n\t"
+        "s_load_dwordx2 %1, %17, 0x8\n\t"
+        "s_load_dwordx2 %2, %17, 0x10\n\t"
+        "s_load_dwordx2 %3, %17, 0x18\n\t"
+        "s_load_dwordx2 %4, %17, 0x20\n\t"
+        "s_load_dwordx2 %5, %17, 0x28\n\t"
+        "s_load_dwordx2 %6, %17, 0x30\n\t"
+        "s_load_dwordx2 %7, %17, 0x38\n\t"
+        "s_load_dwordx2 %8, %17, 0x40\n\t"
+        "s_load_dwordx2 %9, %18, 0x0\n\t"
+        "s_load_dwordx2 %10, %18, 0x8\n\t"
+        "s_load_dwordx2 %11, %18, 0x10\n\t"
+        "s_load_dwordx2 %12, %18, 0x18\n\t"
+        "s_load_dwordx2 %13, %18, 0x20\n\t"
+        "s_load_dwordx2 %14, %18, 0x28\n\t"
+        "s_load_dwordx2 %15, %18, 0x30\n\t"
+        "s_load_dwordx2 %16, %18, 0x38\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "=&s"(p0), "=&s"(p1), "=&s"(p2), "=&s"(p3), "=&s"(p4), "=&s"(p5), "=&s"(p6), "=&s"(p7),
+          "=&s"(p8), "=&s"(o0), "=&s"(o1), "=&s"(o2), "=&s"(o3), "=&s"(o4), "=&s"(o5), "=&s"(o6),
+          "=&s"(o7)
+        : "s"(pre), "s"(off)
+        : "memory");
+    return SegBounds{p0, p1, p2, p3, p4, p5, p6, p7, p8, o0, o1, o2, o3, o4, o5, o6, o7};
+}
+
+__device__ __forceinline__ int64_t uniform_i64(int64_t x) {
+    return (int64_t)(((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32)) << 32) |
+                     (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)x));
+}
+
+// The regions of one sub-tile [b0, b0 + lim): region k of the window starts
+// at sub-tile position rk (wave-uniform, clamped into [0, lim]; r0 = 0) and
+// its element at sub-tile position o sits ak + o sizeof(T) bytes into the
+// item array; r8 >= 1 is where the window's cover of the sub-tile ends.  The
+// ak sit in the first kSegK lanes of one register pair and a lane reads its
+// region's by a lane permute: kSegK 64-bit values to select from directly
+// cost every lane 16 registers (a select reads at most one scalar register)
+// and the scatter at 8 items per thread spilled.
+struct SegWindow {
+    uint32_t tl, th;  // lane k < kSegK holds ak (low, high word)
+    uint32_t r1, r2, r3, r4, r5, r6, r7, r8;
+    bool covered;  // r8 == lim: every position resolves inside the window
+};
+
 // Items of S per-workgroup regions read as one sequence: element i lives in
-// region s with pre[s] <= i < pre[s + 1], at a[off[s] + i - pre[s]].  Each
-// thread walks increasing i, so the region found last is cached in
-// registers and the binary search runs only when i leaves it.  Digit =
-// pk >> shift (partition-key ranges).
+// region s with pre[s] <= i < pre[s + 1], at a[off[s] + i - pre[s]]
+// (S >= kSegK).  Digit = pk >> shift (partition-key ranges).
+//
+// Fast path (window / fetch_sub / hist_sub): the region l0 of a sub-tile's
+// first index is carried from the previous sub-tile or found by a
+// wave-parallel search (find), the next kSegK boundaries and offsets are
+// read into scalar registers, and every lane picks its region with kSegK - 1
+// compares and a lane permute: all loads of a sub-tile are issued together,
+// no branch, search or wait between them.  The window ends at the last
+// region at the latest, so every boundary it reads exists; a position past
+// its cover is clamped into it, so every item address lies in an existing
+// region.  A sub-tile that spans more than kSegK regions (small inputs
+// leave most regions empty) takes the per-lane fetch: each thread walks
+// increasing i, the region found last is cached in registers and the binary
+// search runs only when i leaves it.
 template <class T>
 struct SrcSeg {
     static constexpr bool kDigitFromRec = true;
+    static constexpr bool kRegions = true;
     using Raw = T;
     const T *a;
     const int64_t *pre;  // [S + 1]
     const int64_t *off;  // [S]
     uint32_t S;
     uint32_t shift;
+    // [2] debug counters: sub-tiles scattered by the fast path / by the
+    // per-lane fallback
+    uint32_t *paths = nullptr;
     int64_t lo = 0, hi = 0, base = 0;  // cached region [lo, hi), a index = base + i
+    // the region of flat index hint_b, from the previous window (uniform)
+    int64_t hint_b = -1;
+    uint32_t hint_l = 0;
+    // The largest l < S with pre[l] <= b, for a uniform b < pre[S]: every
+    // round the 64 lanes probe the range at even steps (3 rounds at S = 5121).
+    __device__ __forceinline__ uint32_t find(int64_t b) const {
+        uint32_t l = 0, h = S;
+        const uint32_t lane = __lane_id();
+        while (h - l > 1) {  // pre[l] <= b; h == S or pre[h] > b
+            const uint32_t step = (h - l + 63) >> 6;
+            const uint32_t m = l + lane * step;
+            const bool le = m < h && pre[min(m, h - 1)] <= b;
+            // lane 0 probes l: c >= 1; the lanes that hold are a prefix
+            const uint32_t c = __builtin_amdgcn_readfirstlane((uint32_t)__popcll(__ballot(le)));
+            h = min(h, l + c * step);
+            l = l + (c - 1) * step;
+        }
+        return l;
+    }
+    // next: the first index of the sub-tile the caller visits next (the hint)
+    __device__ __forceinline__ SegWindow window(int64_t b0, uint32_t lim, int64_t next) {
+        const uint32_t l0 = b0 == hint_b ? hint_l : find(b0);
+        // the window starts at l0, or ends at the last region
+        const uint32_t lb = min(l0, S - (uint32_t)kSegK);
+        const SegBounds g = sload_regions(uniform_ptr(pre + lb), uniform_ptr(off + lb));
+        auto addr = [&](int64_t o, int64_t p) { return (uint64_t)(o - p + b0) * sizeof(T); };
+        auto rel = [&](int64_t p) {
+            return (uint32_t)min<int64_t>(max<int64_t>(p - b0, 0), (int64_t)lim);
+        };
+        SegWindow w;
+        // (r0 = 0: p0 <= pre[l0] <= b0)
+        const uint64_t ak[kSegK] = {addr(g.o0, g.p0), addr(g.o1, g.p1), addr(g.o2, g.p2),
+                                    addr(g.o3, g.p3), addr(g.o4, g.p4), addr(g.o5, g.p5),
+                                    addr(g.o6, g.p6), addr(g.o7, g.p7)};
+        const uint32_t lane = __lane_id();
+        uint32_t tl = 0, th = 0;
+#pragma unroll
+        for (int k = 0; k < kSegK; ++k) {
+            tl = lane == (uint32_t)k ? (uint32_t)ak[k] : tl;
+            th = lane == (uint32_t)k ? (uint32_t)(ak[k] >> 32) : th;
+        }
+        w.tl = tl;
+        w.th = th;
+        w.r1 = rel(g.p1);
+        w.r2 = rel(g.p2);
+        w.r3 = rel(g.p3);
+        w.r4 = rel(g.p4);
+        w.r5 = rel(g.p5);
+        w.r6 = rel(g.p6);
+        w.r7 = rel(g.p7);
+        w.r8 = rel(g.p8);  // p8 >= pre[l0 + 1] > b0: r8 >= 1
+        w.covered = g.p8 - b0 >= (int64_t)lim;
+        auto le = [&](int64_t p) { return p <= next ? 1u : 0u; };
+        const uint32_t k = le(g.p1) + le(g.p2) + le(g.p3) + le(g.p4) + le(g.p5) + le(g.p6) + le(g.p7);
+        hint_b = g.p8 > next ? next : -1;
+        hint_l = lb + k;
+        return w;
+    }
+    // address of sub-tile position o (any o: clamped into the window's cover,
+    // so the address is that of an item of an existing region)
+    __device__ __forceinline__ const char *locate(const SegWindow &w, uint32_t o) const {
+        o = min(o, w.r8 - 1u);
+        const uint32_t k = (o >= w.r1 ? 1u : 0u) + (o >= w.r2 ? 1u : 0u) + (o >= w.r3 ? 1u : 0u) +
+                           (o >= w.r4 ? 1u : 0u) + (o >= w.r5 ? 1u : 0u) + (o >= w.r6 ? 1u : 0u) +
+                           (o >= w.r7 ? 1u : 0u);
+        const uint32_t xl = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(k << 2), (int)w.tl);
+        const uint32_t xh = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(k << 2), (int)w.th);
+        const uint64_t x = ((uint64_t)xh << 32) | xl;
+        return reinterpret_cast<const char *>(a) + (x + (uint64_t)o * sizeof(T));
+    }
+    // All loads of a sub-tile, element j at sub-tile position pos(j), issued
+    // together; false: the window does not cover the sub-tile and the caller
+    // loads it again with fetch (the loads issued here stay inside the cover).
+    template <int N, class Pos>
+    __device__ __forceinline__ bool fetch_sub(int64_t b0, uint32_t lim, int64_t next, Pos pos,
+                                              T (&raw)[N]) {
+        const SegWindow w = window(b0, lim, next);
+#pragma unroll
+        for (int j = 0; j < N; ++j) raw[j] = *reinterpret_cast<const T *>(locate(w, pos(j)));
+        // the loads stay here: without this the compiler moved them past the
+        // caller's write-out (stores of another type) to the first use of raw[]
+        asm volatile("" ::: "memory");
+        return w.covered;
+    }
+    // the same for the histogram: the partition keys only
+    template <int N, class Pos>
+    __device__ __forceinline__ bool hist_sub(int64_t b0, uint32_t lim, int64_t next, Pos pos,
+                                             uint32_t (&d)[N]) {
+        const SegWindow w = window(b0, lim, next);
+        uint32_t pk[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) pk[j] = reinterpret_cast<const T *>(locate(w, pos(j)))->pk;
+#pragma unroll
+        for (int j = 0; j < N; ++j) d[j] = pk[j] >> shift;
+        return w.covered;
+    }
     __device__ __forceinline__ T fetch(int64_t i) {
         if (i < lo || i >= hi) {
             uint32_t l = 0, h = S;
@@ -338,6 +533,10 @@ struct SrcSeg {
         return a[base + i];
     }
     __device__ __forceinline__ uint32_t digit(const T &r) const { return r.pk >> shift; }
+    // the digit from a record's first word (the write-out reads staged words:
+    // a record rebuilt from them there went through scratch)
+    static_assert(offsetof(T, pk) == 0, "the partition key is an item's first word");
+    __device__ __forceinline__ uint32_t digit_word0(uint32_t pk) const { return pk >> shift; }
     __device__ __forceinline__ bool decode(const T &x, int64_t, T &r, uint32_t &d) const {
         r = x;
         d = digit(x);
@@ -532,6 +731,31 @@ __global__ __launch_bounds__(kPartThreads) void k_hist(Src src_in, const TileDes
                 hist[(size_t)t * F + d] = lh[d] + lh[F + d] + lh[2 * F + d] + lh[3 * F + d];
             return;
         }
+    }
+    if constexpr (HasRegions<Src>::value) {
+        // region sources: the regions of each round of U kPartThreads indices
+        // are resolved once, uniformly, and its U loads are issued together;
+        // a round that spans more regions than the window holds is counted
+        // by the per-lane lookup
+        const int64_t tb = uniform_i64(td.begin), te = uniform_i64(td.end);
+        for (int64_t b = tb; b < te; b += U * kPartThreads) {
+            const uint32_t lim = (uint32_t)min<int64_t>(U * kPartThreads, te - b);
+            uint32_t d[U];
+            const bool fast = src.hist_sub(b, lim, b + U * kPartThreads,
+                                           [tid](int u) { return (uint32_t)(u * kPartThreads + tid); }, d);
+            if (!fast) {
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    (void)src.hist(b + min((uint32_t)(u * kPartThreads + tid), lim - 1), d[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if ((uint32_t)(u * kPartThreads + tid) < lim) atomicAdd(&my[d[u]], 1u);
+        }
+        __syncthreads();
+        for (uint32_t d = tid; d < F; d += kPartThreads)
+            hist[(size_t)t * F + d] = lh[d] + lh[F + d] + lh[2 * F + d] + lh[3 * F + d];
+        return;
     }
     int64_t i = td.begin + tid;
     for (; i + (U - 1) * kPartThreads < td.end; i += U * kPartThreads) {
@@ -1036,16 +1260,6 @@ __device__ unsigned long long g_scat_cyc[8];
     } while (0)
 #endif
 
-// A pointer made provably uniform (scalar-load operands: dpg_team.h
-// sload_desc; a pointer the compiler keeps in vector registers is not one).
-template <class T>
-__device__ __forceinline__ const T *uniform_ptr(const T *p) {
-    const uint64_t v = (uint64_t)(uintptr_t)p;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<const T *>((uintptr_t)(((uint64_t)hi << 32) | lo));
-}
-
 // kAgg: wave-aggregated ranking (few digits) instead of one LDS atomic per
 // record; a template parameter so that each kernel holds one ranking path
 // (both paths in one kernel cost the hot one its registers)
@@ -1120,6 +1334,10 @@ __global__ __launch_bounds__(NT, 4) void k_scatter(Src src_in, const TileDesc *t
     // 16-byte load (clamped to the last two records; a one-record sub-tile
     // loads singly)
     typename Src::Raw raw[IPT];
+    // region sources (SrcSeg): raw[] holds the sub-tile (its regions fit the
+    // window); false: the sub-tile is loaded again by the per-lane lookup
+    constexpr bool kSeg = HasRegions<Src>::value;
+    bool seg_fast = true;
     auto load_sub = [&](int64_t b0, uint32_t lim) {
         if constexpr (kEarly) {
             // the pairs as loaded, for any lim >= 1: lim == 1 loads the
@@ -1145,6 +1363,13 @@ __global__ __launch_bounds__(NT, 4) void k_scatter(Src src_in, const TileDesc *t
                 }
                 return;
             }
+        }
+        if constexpr (kSeg) {
+            // region sources: the sub-tile's regions resolved once, uniformly,
+            // and all its loads issued together; whether they cover the
+            // sub-tile is acted on where raw[] is decoded
+            seg_fast = src.fetch_sub(b0, lim, b0 + SUB, elem, raw);
+            return;
         }
 #pragma unroll
         for (int j = 0; j < IPT; ++j) raw[j] = src.fetch(b0 + min(elem(j), lim - 1));
@@ -1237,6 +1462,15 @@ __global__ __launch_bounds__(NT, 4) void k_scatter(Src src_in, const TileDesc *t
         const uint32_t lim = (uint32_t)min<int64_t>(SUB, td.end - sb);  // uniform
         Rec rec[IPT];
         uint32_t dr[IPT];  // digit | rank << 12, or ~0 for a dropped record
+        if constexpr (kSeg) {
+            // (uniform) more regions than the window holds: the per-lane
+            // lookup loads the sub-tile
+            if (!seg_fast) {
+#pragma unroll
+                for (int j = 0; j < IPT; ++j) raw[j] = src.fetch(sb + min(elem(j), lim - 1));
+            }
+            if (src.paths && tid == 0) atomicAdd(&src.paths[seg_fast ? 0 : 1], 1u);
+        }
         if constexpr (!kAgg) {
             // wide fan-out: one LDS atomic per record ranks it (order inside
             // a digit is free); all IPT atomics are in flight together, a
@@ -1387,21 +1621,37 @@ __global__ __launch_bounds__(NT, 4) void k_scatter(Src src_in, const TileDesc *t
         // slots past the end repeat the last staged record, whose store they
         // duplicate (same value, same address)
         constexpr int WB = IPT < DPG_SCAT_WB ? IPT : DPG_SCAT_WB;
-        // piece mode: a fixed trip count, fully unrolled -- as a loop, the
+        // piece mode and region sources: a fixed trip count, fully unrolled -- as a loop, the
         // compiler's loop-preheader vmcnt flush (a loop with stores, no loads,
         // using a register it still counts as loaded outside) waited for the
         // prefetched loads just issued before the first store
         constexpr int kWbIter = (IPT + WB - 1) / WB;
         auto write_batch = [&](uint32_t k0) {
             W x[WB];
+            static_assert(!kSeg || sizeof(W) / W::N >= 8, "items are read as 8- or 16-byte words");
+            using NV = std::conditional_t<sizeof(W) / W::N == 16, u32x4, u32x2>;
+            NV xv[WB][W::N];  // region sources
             uint32_t dd[WB], kc[WB];
 #pragma unroll
             for (int u = 0; u < WB; ++u) {
                 kc[u] = min(k0 + u * NT + tid, total - 1);
-                x[u] = stage[kc[u]];
+                if constexpr (kSeg) {
+                    // as native vectors: the digit below reads part of x[u],
+                    // and a struct copy read in part kept the rest in scratch
+#pragma unroll
+                    for (int q = 0; q < W::N; ++q)
+                        xv[u][q] = reinterpret_cast<const NV *>(&stage[kc[u]])[q];
+                } else {
+                    x[u] = stage[kc[u]];
+                }
                 if constexpr (kSD) dd[u] = sdig[kc[u]];
             }
-            if constexpr (!kSD) {
+            if constexpr (kSeg) {
+#pragma unroll
+                for (int u = 0; u < WB; ++u) {
+                    dd[u] = src.digit_word0(xv[u][0].x);
+                }
+            } else if constexpr (!kSD) {
 #pragma unroll
                 for (int u = 0; u < WB; ++u) dd[u] = src.digit(from_words<Rec>(x[u]));
             }
@@ -1424,10 +1674,18 @@ __global__ __launch_bounds__(NT, 4) void k_scatter(Src src_in, const TileDesc *t
             }
 #else
 #pragma unroll
-            for (int u = 0; u < WB; ++u) *reinterpret_cast<W *>(&out[c1[u] - c2[u] + kc[u]]) = x[u];
+            for (int u = 0; u < WB; ++u) {
+                W *dst = reinterpret_cast<W *>(&out[c1[u] - c2[u] + kc[u]]);
+                if constexpr (kSeg) {
+#pragma unroll
+                    for (int q = 0; q < W::N; ++q) reinterpret_cast<NV *>(dst)[q] = xv[u][q];
+                } else {
+                    *dst = x[u];
+                }
+            }
 #endif
         };
-        if constexpr (kPc) {
+        if constexpr (kPc || kSeg) {
 #pragma unroll
             for (int b = 0; b < kWbIter; ++b) {
                 if ((uint32_t)b * WB * NT >= total) break;
