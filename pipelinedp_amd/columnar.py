@@ -34,6 +34,14 @@ SHARDING_MODES = ("trusted", "verify", "shuffle")
 class ColumnarData:
     """Columnar collection for DPEngine.aggregate on the MI355X backend.
 
+    `pid`, `pk`, `value`: torch tensors, numpy arrays or lists.  A column may
+    be any strided view on any device (`table[:, j]`, `buf[1:]`, `x[::2]`):
+    the encoder makes it a contiguous device column, copying only when it is
+    not one already.  Integer columns of any width are widened to int64, float
+    columns converted to float64; a scalar-metric `value` may be [n] or
+    [n, 1].  The lengths must agree: a `pid` or `value` whose length differs
+    from `pk`'s raises ValueError on the host.
+
     `n_partitions`: if given, `pk` must already hold dense ids in
     [0, n_partitions) and is passed to the device unchecked (the kernel still
     rejects out-of-range keys with ValueError).
@@ -165,6 +173,23 @@ def _to_tensor(x, device) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a)).to(device)
 
 
+def _length(x) -> int:
+    try:
+        return len(x)
+    except TypeError:
+        return int(np.asarray(x).shape[0])
+
+
+def _check_length(name: str, x, n: int) -> None:
+    """A column shorter than pk would be read past its end by the kernels
+    (they take n = len(pk) and raw pointers); a longer one is a caller error
+    too.  Host only: nothing is copied or launched before this."""
+    m = _length(x)
+    if m != n:
+        raise ValueError(f"column {name} has {m} elements but pk has {n}: "
+                         f"the columns of one collection must have the same length")
+
+
 def _integer_like(x) -> bool:
     if isinstance(x, torch.Tensor):
         return not x.is_floating_point() and not x.is_complex() and x.dtype != torch.bool
@@ -293,7 +318,12 @@ def _range(t: torch.Tensor):
 
 def encode(col, extractors, device: torch.device, need_values: bool,
            public_partitions=None, need_pid: bool = True,
-           allow_sparse: bool = False) -> EncodedInput:
+           allow_sparse: bool = False, vector_size: Optional[int] = None) -> EncodedInput:
+    """Every returned column is contiguous (a copy only when the caller's is
+    not), int64 / float64, on `device`, and n elements long: the kernels take
+    raw pointers.  `vector_size`: None for scalar metrics, whose value column
+    is [n] (or [n, 1], flattened; another shape raises ValueError); with
+    VECTOR_SUM the [n, vector_size] shape is the caller's to check."""
     pid_range, rec_off = None, 0
     if _is_columnar(col):
         pid = _extract(col, extractors.privacy_id_extractor) if need_pid else None
@@ -315,6 +345,11 @@ def encode(col, extractors, device: torch.device, need_values: bool,
     n = len(pk)
     if need_values and value is None:
         raise ValueError("value_extractor must be set for SUM, MEAN and VARIANCE")
+    # the kernels read n elements of every column through a raw pointer
+    if need_pid and pid is not None:
+        _check_length("pid", pid, n)
+    if need_values:
+        _check_length("value", value, n)
 
     # ---- partition keys -> dense ids
     # dense integer keys with a declared P and array-like public partitions:
@@ -430,6 +465,14 @@ def encode(col, extractors, device: torch.device, need_values: bool,
     val = None
     if need_values:
         val = _to_tensor(value, device).to(torch.float64)
+        if vector_size is None:
+            if val.dim() == 2 and val.shape[1] == 1:
+                val = val.reshape(-1)
+            elif val.dim() != 1:
+                raise ValueError(
+                    f"the value column has shape {tuple(val.shape)}: SUM, MEAN, VARIANCE and "
+                    f"PERCENTILE need one value per record, shape ({n},) or ({n}, 1)")
+        val = val.contiguous()
 
     enc = EncodedInput(pid=pid_ids, pk=pk_ids.contiguous(), value=val, n=n,
                        n_partitions=int(P), key_table=key_table, pid_min=pid_min,

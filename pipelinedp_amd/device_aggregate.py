@@ -352,7 +352,8 @@ class DeviceAggregation:
                 "(ColumnarData(n_partitions=P))")
         enc = columnar.encode(self.col, self.extractors, dev, need_values,
                               self.public_partitions,
-                              need_pid=not self.bounds_already_enforced, allow_sparse=True)
+                              need_pid=not self.bounds_already_enforced, allow_sparse=True,
+                              vector_size=self.plan.vector_size if self.plan is not None else None)
         if enc.pk_sparse:
             self._encode_sparse_keys(enc)
         if self.bounds_already_enforced:

@@ -106,3 +106,124 @@ def test_numpy_scalar_key_list_with_declared_partitions_stays_dense():
     enc = columnar.encode([(1, np.int64(3), 1.0), (2, np.int64(9), 2.0)], EX, CPU, True)
     assert enc.key_table is not None
     assert [type(k) for k in enc.key_table] == [np.int64, np.int64]
+
+
+# ---- memory layouts: the kernels take raw pointers, so every column encode()
+# returns is contiguous, int64 / float64 and n long, whatever view came in
+from tests import layouts  # noqa: E402
+
+_N = 10
+_PID = np.array([7, 3, 7, 9, 1, 3, 3, 8, 2, 7])
+_PK = np.array([4, 0, 2, 2, 5, 1, 0, 3, 5, 4])
+_VAL = np.array([0.5, -1.25, 3.0, 7.75, 2.0, 9.5, -4.0, 6.25, 1.0, 8.0])
+_COLS = pdp.DataExtractors("pid", "pk", "value")
+
+
+def _make(a, layout, lib):
+    return (layouts.torch_view if lib == "torch" else layouts.numpy_view)(a, layout)
+
+
+def _assert_encoded(enc, pid, pk, value):
+    """pid / pk / value: the views that went in (their logical content is the
+    expectation, as np.ascontiguousarray gives it)."""
+    for got, view, dtype in ((enc.pid, pid, torch.int64), (enc.pk, pk, torch.int64),
+                             (enc.value, value, torch.float64)):
+        want = np.ascontiguousarray(view.numpy() if isinstance(view, torch.Tensor) else view)
+        assert got.is_contiguous()
+        assert got.dtype == dtype
+        assert got.shape == (_N,)
+        assert np.array_equal(got.numpy(), want.reshape(-1).astype(got.numpy().dtype))
+    assert enc.n == _N
+
+
+@pytest.mark.parametrize("lib", ["torch", "numpy"])
+@pytest.mark.parametrize("kdtype,vdtype", [("int64", "float64"), ("int32", "float32")])
+@pytest.mark.parametrize("which", ["pid", "pk", "value", "all"])
+@pytest.mark.parametrize("layout", layouts.LAYOUTS)
+def test_strided_and_offset_columns_are_encoded_contiguous(layout, which, kdtype, vdtype, lib):
+    base = dict(pid=_PID.astype(kdtype), pk=_PK.astype(kdtype), value=_VAL.astype(vdtype))
+    cols = {k: _make(a, layout if which in (k, "all") else "contiguous", lib)
+            for k, a in base.items()}
+    if layout != "contiguous" and lib == "torch":
+        for k in cols:
+            if which in (k, "all"):
+                assert not cols[k].is_contiguous() or cols[k].storage_offset() == 1
+    # privacy ids: with n_partitions the caller's ids pass through as they are
+    enc = columnar.encode(pdp.ColumnarData(**cols, n_partitions=6), _COLS, CPU, True)
+    _assert_encoded(enc, cols["pid"], cols["pk"], cols["value"])
+    # a mapping of columns takes the same path
+    enc = columnar.encode(dict(cols, n_partitions=6), _COLS, CPU, True)
+    _assert_encoded(enc, cols["pid"], cols["pk"], cols["value"])
+
+
+@pytest.mark.parametrize("lib", ["torch", "numpy"])
+@pytest.mark.parametrize("kdtype,vdtype", [("int64", "float64"), ("int32", "float32")])
+def test_expanded_and_two_dimensional_columns(kdtype, vdtype, lib):
+    # stride 0: n copies of one element, for every column
+    cols = dict(pid=layouts.expanded(5, _N, lib, kdtype), pk=layouts.expanded(2, _N, lib, kdtype),
+                value=layouts.expanded(1.5, _N, lib, vdtype))
+    enc = columnar.encode(pdp.ColumnarData(**cols, n_partitions=6), _COLS, CPU, True)
+    _assert_encoded(enc, cols["pid"], cols["pk"], cols["value"])
+    assert enc.pid.tolist() == [5] * _N and enc.value.tolist() == [1.5] * _N
+    # a scalar-metric value column of shape [n, 1] is flattened
+    cols = dict(pid=_make(_PID.astype(kdtype), "contiguous", lib),
+                pk=_make(_PK.astype(kdtype), "contiguous", lib),
+                value=_make(_VAL.astype(vdtype), "col2d", lib))
+    assert tuple(cols["value"].shape) == (_N, 1)
+    enc = columnar.encode(pdp.ColumnarData(**cols, n_partitions=6), _COLS, CPU, True)
+    _assert_encoded(enc, cols["pid"], cols["pk"], cols["value"])
+    # ... also as the second column of a wider table, [n, 1] with a row stride
+    if lib == "torch":
+        wide = torch.from_numpy(np.stack([_VAL + 1000, _VAL, _VAL + 1000], 1).astype(vdtype))
+    else:
+        wide = np.stack([_VAL + 1000, _VAL, _VAL + 1000], 1).astype(vdtype)
+    cols["value"] = wide[:, 1:2]
+    enc = columnar.encode(pdp.ColumnarData(**cols, n_partitions=6), _COLS, CPU, True)
+    _assert_encoded(enc, cols["pid"], cols["pk"], cols["value"])
+
+
+@pytest.mark.parametrize("lib", ["torch", "numpy", "list"])
+@pytest.mark.parametrize("column,m", [("pid", 5), ("value", 5), ("value", 15), ("pid", 15)],
+                         ids=["short_pid", "short_value", "long_value", "long_pid"])
+def test_length_mismatch_raises(column, m, lib):
+    base = dict(pid=np.arange(15) % 7, pk=np.arange(15) % 6, value=np.arange(15) * 0.5)
+    cols = {k: a[:m if k == column else _N] for k, a in base.items()}
+    if lib == "torch":
+        # views of longer tables, as a caller would hold them
+        cols = {k: torch.from_numpy(np.stack([a, a], 1))[:, 0] for k, a in cols.items()}
+    elif lib == "list":
+        cols = {k: a.tolist() for k, a in cols.items()}
+    with pytest.raises(ValueError, match=rf"{column} has {m} elements but pk has {_N}"):
+        columnar.encode(pdp.ColumnarData(**cols, n_partitions=6), _COLS, CPU, True)
+    with pytest.raises(ValueError, match=rf"{column} has {m} elements but pk has {_N}"):
+        columnar.encode(pdp.ColumnarData(**cols), _COLS, CPU, True)
+    # a column that is not read is not checked
+    enc = columnar.encode(pdp.ColumnarData(**cols, n_partitions=6), _COLS, CPU,
+                          need_values=column != "value", need_pid=column != "pid")
+    assert enc.n == _N
+
+
+def test_length_mismatch_is_raised_before_any_device_call():
+    """The check needs no device: a device that does not exist is never
+    touched (torch would raise RuntimeError / AssertionError on the copy)."""
+    cols = pdp.ColumnarData(pid=np.arange(10), pk=np.arange(10) % 6, value=np.ones(5),
+                            n_partitions=6)
+    with pytest.raises(ValueError, match="value has 5 elements but pk has 10"):
+        columnar.encode(cols, _COLS, torch.device("cuda", 63), True)
+
+
+@pytest.mark.parametrize("shape", [(_N, 2), (_N, 1, 1), (2, 5)])
+def test_non_scalar_value_shape_raises_for_scalar_metrics(shape):
+    value = torch.zeros(shape, dtype=torch.float64)
+    cols = pdp.ColumnarData(pid=torch.arange(_N), pk=torch.arange(_N) % 6, value=value,
+                            n_partitions=6)
+    with pytest.raises(ValueError):
+        columnar.encode(cols, _COLS, CPU, True)
+    if shape == (_N, 2):
+        # VECTOR_SUM's own shape check is the plan's (TypeError, "Shape mismatch"):
+        # encode leaves an [n, D] column as it is, contiguous
+        t = torch.zeros((_N, 4), dtype=torch.float64)[:, 1:3]
+        cols = pdp.ColumnarData(pid=torch.arange(_N), pk=torch.arange(_N) % 6, value=t,
+                                n_partitions=6)
+        enc = columnar.encode(cols, _COLS, CPU, True, vector_size=2)
+        assert enc.value.shape == (_N, 2) and enc.value.is_contiguous()
