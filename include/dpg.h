@@ -636,6 +636,59 @@ int dpg_keydict_gather_ids(dpg_ctx *ctx, const uint32_t *out_slots, int64_t n,
                            const uint32_t *slot_ids, int64_t capacity, int64_t *out_ids,
                            int64_t *n_missing, void *stream);
 
+/* ---- string columns: bytes to 64-bit keys, checked for collisions ----
+ * A string column (pipelinedp_amd.StringColumn) is Arrow's variable-width
+ * layout: offsets (device int64[n + 1]) and data (device uint8[data_len]);
+ * record i is the bytes data[offsets[i], offsets[i + 1]).  The three calls
+ * below reduce it to what the table calls above take (csrc/dpg_strkey.h;
+ * DESIGN.md section 18): a 64-bit key per record, the first record of every
+ * slot, and the count of records whose bytes differ from that record's -- so
+ * a hash collision is found, never released as one merged partition.
+ *
+ * All three follow the table calls' contract: n < 2^31 (else
+ * DPG_ERR_UNSUPPORTED); n == 0 is a no-op (the per-record pointers may then be
+ * NULL); n < 0, data_len < 0, a bad capacity or a NULL pointer (data may be
+ * NULL when data_len == 0): DPG_ERR_INVALID_ARG; both before any device work.
+ * The counters are added to, so the caller zeroes them.  Stream-ordered, no
+ * host synchronisation.
+ *
+ * The key of a string s of len bytes under a 64-bit seed, with fmix64 as
+ * given with the key dictionary above and all arithmetic modulo 2^64:
+ *   h = fmix64(seed ^ (len * 0x9E3779B97F4A7C15))
+ *   for k = 0 .. ceil(len / 8) - 1:
+ *       w = the bytes s[8k .. 8k + 8) as a little-endian 64-bit word, bytes
+ *           at positions >= len taken as zero
+ *       h = fmix64(h ^ w)
+ *   key = h, except that h == DPG_KEYDICT_EMPTY gives DPG_KEYDICT_EMPTY ^ 1:
+ *   the table's reserved key never comes out.
+ * The empty string has no words: its key is fmix64(seed).
+ *
+ * out_keys[i] (device int64[n]) = the key of record i.  A record whose
+ * offsets are not 0 <= offsets[i] <= offsets[i + 1] <= data_len reads nothing,
+ * gets the key 0 and adds 1 to info[0] (device int64[1]).  No byte outside
+ * data[0, data_len) is read, whatever the alignment of data and of the
+ * strings in it. */
+int dpg_string_hash(dpg_ctx *ctx, const int64_t *offsets, const uint8_t *data, int64_t data_len,
+                    int64_t n, uint64_t seed, int64_t *out_keys, int64_t *info, void *stream);
+/* rep (device uint32[capacity], capacity as for the table, filled with
+ * 0xFFFFFFFF by the caller): afterwards rep[s] is the smallest i < n with
+ * rec_slots[i] == s (rec_slots: device uint32[n], as dpg_keydict_insert_slots
+ * wrote it), and still 0xFFFFFFFF for a slot no record has.  Entries of
+ * rec_slots that are not a slot of the table (0xFFFFFFFF) are skipped.  May be
+ * called several times on one rep: values only fall. */
+int dpg_keydict_representatives(dpg_ctx *ctx, const uint32_t *rec_slots, int64_t n,
+                                int64_t capacity, uint32_t *rep, void *stream);
+/* *n_mismatch (device int64) += the records i < n whose bytes differ from
+ * the bytes of record rep[rec_slots[i]]: length first, then content.  Records
+ * with rec_slots[i] == 0xFFFFFFFF are skipped; every other entry must be a
+ * slot of the table rep belongs to.  Offsets are checked as in
+ * dpg_string_hash: a record with invalid offsets -- its own or its
+ * representative's -- or whose slot has no representative below n counts as a
+ * mismatch and reads nothing. */
+int dpg_string_verify(dpg_ctx *ctx, const int64_t *offsets, const uint8_t *data, int64_t data_len,
+                      int64_t n, const uint32_t *rec_slots, const uint32_t *rep,
+                      int64_t *n_mismatch, void *stream);
+
 /* ---- multi-GPU utility analysis: pairs to the rank that owns their partition ----
  * The per-partition utility combiners need every (privacy id, partition) pair
  * of a partition on one rank, so each rank's pre-aggregate travels to the

@@ -32,6 +32,7 @@ from pipelinedp_amd.pipeline_backend import MI355XBackend
 from pipelinedp_amd.pipeline_backend import PipelineBackend
 from pipelinedp_amd.pipeline_backend import register_annotator
 from pipelinedp_amd.report_generator import ExplainComputationReport
+from pipelinedp_amd.string_columns import StringColumn
 from pipelinedp_amd import dataset_histograms
 
 __version__ = "0.1.0"

@@ -30,7 +30,8 @@ EXPORTED = ("dpg_ctx_create", "dpg_ctx_destroy", "dpg_last_error", "dpg_set_seed
             "dpg_sample_partitions", "dpg_partition_summary",
             "dpg_keydict_insert", "dpg_keydict_keys", "dpg_keydict_assign",
             "dpg_keydict_lookup", "dpg_keydict_insert_slots", "dpg_keydict_gather_ids",
-            "dpg_shard_records_wide", "dpg_check_shard_wide")
+            "dpg_shard_records_wide", "dpg_check_shard_wide",
+            "dpg_string_hash", "dpg_keydict_representatives", "dpg_string_verify")
 
 KEYDICT_EMPTY = 1 << 63  # DPG_KEYDICT_EMPTY: the bit pattern of INT64_MIN, the reserved key
 KEYDICT_NO_SLOT = 0xFFFFFFFF  # dpg_keydict_insert_slots: a reserved or lost record
@@ -294,6 +295,12 @@ def load():
         lib.dpg_shard_records_wide.restype = ctypes.c_int
         lib.dpg_check_shard_wide.argtypes = lib.dpg_check_shard.argtypes
         lib.dpg_check_shard_wide.restype = ctypes.c_int
+        lib.dpg_string_hash.argtypes = [vp, vp, vp, i64, i64, ctypes.c_uint64, vp, vp, vp]
+        lib.dpg_string_hash.restype = ctypes.c_int
+        lib.dpg_keydict_representatives.argtypes = [vp, vp, i64, i64, vp, vp]
+        lib.dpg_keydict_representatives.restype = ctypes.c_int
+        lib.dpg_string_verify.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, vp]
+        lib.dpg_string_verify.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -635,6 +642,32 @@ class Context:
         st = self.lib.dpg_keydict_gather_ids(self.handle, out_slots_ptr, int(n), slot_ids_ptr,
                                              int(capacity), out_ids_ptr, n_missing_ptr, stream)
         self.check(st, "dpg_keydict_gather_ids")
+
+    def string_hash(self, offsets_ptr, data_ptr, data_len, n, seed, out_keys_ptr, info_ptr,
+                    stream):
+        """out_keys[i] (device int64) = the 64-bit key of the string
+        data[offsets[i]:offsets[i + 1]] (the definition is in dpg.h); a record
+        with offsets outside 0 <= start <= end <= data_len gets key 0 and the
+        device int64 at info_ptr += 1."""
+        st = self.lib.dpg_string_hash(self.handle, offsets_ptr, data_ptr, int(data_len), int(n),
+                                      ctypes.c_uint64(int(seed) & (2**64 - 1)), out_keys_ptr,
+                                      info_ptr, stream)
+        self.check(st, "dpg_string_hash")
+
+    def keydict_representatives(self, rec_slots_ptr, n, capacity, rep_ptr, stream):
+        """rep[s] (device uint32[capacity], filled with KEYDICT_NO_SLOT) = the
+        smallest i with rec_slots[i] == s."""
+        st = self.lib.dpg_keydict_representatives(self.handle, rec_slots_ptr, int(n),
+                                                  int(capacity), rep_ptr, stream)
+        self.check(st, "dpg_keydict_representatives")
+
+    def string_verify(self, offsets_ptr, data_ptr, data_len, n, rec_slots_ptr, rep_ptr,
+                      n_mismatch_ptr, stream):
+        """The device int64 at n_mismatch_ptr += records whose bytes differ
+        from those of their slot's representative rep[rec_slots[i]]."""
+        st = self.lib.dpg_string_verify(self.handle, offsets_ptr, data_ptr, int(data_len), int(n),
+                                        rec_slots_ptr, rep_ptr, n_mismatch_ptr, stream)
+        self.check(st, "dpg_string_verify")
 
     def stage_times(self):
         names = ctypes.create_string_buffer(4096)

@@ -38,7 +38,7 @@ def compute_public_partitions_summary(col, backend, extractors, public_partition
     def run():
         dev = backend.device
         enc = columnar.encode(col, extractors, dev, need_values=False, need_pid=False,
-                              public_partitions=public_partitions)
+                              public_partitions=public_partitions, ctx=backend.ctx)
         counts = torch.empty(3, dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
             sptr = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)

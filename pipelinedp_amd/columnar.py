@@ -17,7 +17,10 @@ dictionary-encoded (`unique` + inverse), and the partition dictionary maps
 results back.  Encoding is ingest, not part of the DP computation.
 ColumnarData(wide_privacy_ids=True) leaves int64 privacy ids of any span as
 they are; the device numbers them after the records are placed
-(distributed.encode_privacy_ids).
+(distributed.encode_privacy_ids).  A StringColumn (string_columns.py: offsets
+and bytes) is hashed on the device: as `pk` it gets the dense ids and the
+key table a list of the same strings would get, as `pid` it becomes wide
+privacy ids.
 """
 import dataclasses
 from collections.abc import Mapping
@@ -25,6 +28,9 @@ from typing import Any, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
+
+from . import string_columns
+from .string_columns import StringColumn
 
 _PID_SPAN = 1 << 32  # privacy ids of one call must span at most 2^32 values
 SHARDING_MODES = ("trusted", "verify", "shuffle")
@@ -88,7 +94,23 @@ class ColumnarData:
     distinct privacy ids, which sizes the hash table (else the record count
     does); a bound that is too small raises ValueError on every rank.  With
     contribution_bounds_already_enforced the privacy ids are not read and the
-    flag does nothing."""
+    flag does nothing.
+
+    String columns (opt-in): `pid` and `pk` may each be a StringColumn --
+    Arrow's offsets + bytes layout, ideally already on the GPU -- which the
+    device hashes to 64-bit keys; lists and arrays of
+    `str` keep the host encoding.  A string `pk` is dictionary-encoded on the
+    device, every record compared with the first record of its hash-table slot,
+    so a hash collision raises ValueError ("pass another hash_seed") instead of
+    merging two partitions; results carry the strings, and the public
+    partitions are then a list or tuple of `str` or a StringColumn.
+    `max_distinct_partition_keys` sizes its table too.  It runs in one process
+    (several ranks: NotImplementedError) and excludes `n_partitions` and
+    `sparse_partition_keys` (ValueError).  A string `pid` becomes wide privacy
+    ids -- the hashes -- with everything said above about them, on one rank or
+    several; a caller who pre-shards for "trusted" uses
+    distributed.shard_of_wide(distributed.string_key_hash(column), R).
+    `privacy_id_range` must not be given (ValueError)."""
     pid: Any = None
     pk: Any = None
     value: Any = None
@@ -111,8 +133,10 @@ class ColumnarData:
             if self.privacy_id_range is not None:
                 raise ValueError("wide_privacy_ids=True encodes the privacy ids itself: "
                                  "privacy_id_range must not be given")
-            if self.pid is not None:
+            if self.pid is not None and not isinstance(self.pid, StringColumn):
                 _check_wide_pid(self.pid)
+        _check_string_columns(self.pid, self.pk, self.n_partitions, self.sparse_partition_keys,
+                              self.privacy_id_range)
 
     def __getitem__(self, name):
         return getattr(self, name)
@@ -152,6 +176,10 @@ class EncodedInput:
     # rank's dense ids; max_distinct_pids sizes its table
     pid_wide: bool = False
     max_distinct_pids: Optional[int] = None
+    # a StringColumn of privacy ids: pid holds its hashes (pid_wide) and this
+    # device int64[1] the records whose offsets were invalid, which
+    # distributed.encode_privacy_ids raises for on every rank alike
+    pid_bad_offsets: Optional[torch.Tensor] = None
 
 
 def _extract(col, extractor):
@@ -200,6 +228,20 @@ def _check_wide_pid(pid) -> None:
     if not (isinstance(pid, (torch.Tensor, np.ndarray)) and _integer_like(pid)):
         raise TypeError("wide_privacy_ids=True needs integers: an integer tensor or array of "
                         "privacy ids")
+
+
+def _check_string_columns(pid, pk, n_partitions, sparse, pid_range) -> None:
+    """The options a StringColumn excludes; host state only."""
+    if isinstance(pk, StringColumn):
+        if n_partitions is not None:
+            raise ValueError("a StringColumn of partition keys gets its dense ids from the "
+                             "device dictionary: n_partitions must not be given")
+        if sparse:
+            raise ValueError("sparse_partition_keys=True needs integer partition keys, not a "
+                             "StringColumn (which has a device dictionary of its own)")
+    if isinstance(pid, StringColumn) and pid_range is not None:
+        raise ValueError("a StringColumn of privacy ids is hashed to wide privacy ids: "
+                         "privacy_id_range must not be given")
 
 
 def _is_int_key(k) -> bool:
@@ -318,8 +360,11 @@ def _range(t: torch.Tensor):
 
 def encode(col, extractors, device: torch.device, need_values: bool,
            public_partitions=None, need_pid: bool = True,
-           allow_sparse: bool = False, vector_size: Optional[int] = None) -> EncodedInput:
-    """Every returned column is contiguous (a copy only when the caller's is
+           allow_sparse: bool = False, vector_size: Optional[int] = None,
+           ctx=None, world_size: int = 1) -> EncodedInput:
+    """`ctx`: the library context of the backend, which a StringColumn needs
+    (NotImplementedError without); `world_size`: the backend's, since a string
+    `pk` runs in one process only.  Every returned column is contiguous (a copy only when the caller's is
     not), int64 / float64, on `device`, and n elements long: the kernels take
     raw pointers.  `vector_size`: None for scalar metrics, whose value column
     is [n] (or [n, 1], flattened; another shape raises ValueError); with
@@ -351,12 +396,31 @@ def encode(col, extractors, device: torch.device, need_values: bool,
     if need_values:
         _check_length("value", value, n)
 
+    # ---- string columns: what they exclude, from host state only (so every
+    # rank raises alike, before any device work or collective)
+    str_pk = isinstance(pk, StringColumn)
+    str_pid = need_pid and isinstance(pid, StringColumn)
+    if str_pk or str_pid:
+        _check_string_columns(pid if str_pid else None, pk, hint,
+                              isinstance(col, ColumnarData) and col.sparse_partition_keys,
+                              pid_range)
+        if ctx is None:
+            raise NotImplementedError("a StringColumn is encoded on the device: this entry "
+                                      "point does not pass the library context to the encoder")
+    if str_pk and world_size > 1:
+        raise NotImplementedError(
+            "a StringColumn of partition keys is supported in one process only: a global "
+            "string dictionary across ranks is not built.  Encode the partition keys to dense "
+            "ids (ColumnarData(n_partitions=P)) or to int64 keys (sparse_partition_keys=True)")
+    if isinstance(public_partitions, StringColumn) and not str_pk:
+        public_partitions = public_partitions.to_strings()
+
     # ---- partition keys -> dense ids
     # dense integer keys with a declared P and array-like public partitions:
     # the public bitmap is built on the device (config 4: 1e8 public ids)
     pub_dense = None
     pub_range = None  # a unit-step range: its bitmap is two partial bytes and a fill
-    if public_partitions is not None and hint is not None and _integer_like(pk):
+    if public_partitions is not None and hint is not None and not str_pk and _integer_like(pk):
         if isinstance(public_partitions, range) and public_partitions.step == 1:
             pub_range = (public_partitions.start, public_partitions.stop)
         else:
@@ -379,7 +443,7 @@ def encode(col, extractors, device: torch.device, need_values: bool,
         if public_partitions is not None:
             sparse_public = _sparse_public_keys(public_partitions, device)
     public_list = (None if public_partitions is None or pub_dense is not None
-                   or pub_range is not None or sparse else list(public_partitions))
+                   or pub_range is not None or sparse or str_pk else list(public_partitions))
     key_table = None
     pk_ids = None
     public_ids = None
@@ -391,7 +455,14 @@ def encode(col, extractors, device: torch.device, need_values: bool,
     # built over those ids, so they must not be re-encoded
     np_row_keys = (hint is None and not sparse and isinstance(pk, list)
                    and any(isinstance(k, np.generic) for k in pk))
-    if _integer_like(pk) and not np_row_keys:
+    if str_pk:
+        # hashed, verified and dictionary-encoded on the device; only the
+        # distinct strings reach the host
+        pk_ids, key_table, public_ids = string_columns.encode_partition_keys(
+            pk, string_columns.public_strings(public_partitions), device, ctx,
+            col.max_distinct_partition_keys if isinstance(col, ColumnarData) else None)
+        P = max(len(key_table), 1)
+    elif _integer_like(pk) and not np_row_keys:
         pk_t = _to_tensor(pk, device).to(torch.int64)
         if sparse:
             pk_ids, P = pk_t, 1  # P: a placeholder until the dictionary is built
@@ -431,10 +502,19 @@ def encode(col, extractors, device: torch.device, need_values: bool,
     # distributed.encode_privacy_ids builds the rank's dictionary once the
     # records are placed
     wide = need_pid and isinstance(col, ColumnarData) and col.wide_privacy_ids
+    pid_bad_offsets = None
     if need_pid:
         if pid is None:
             raise ValueError("privacy_id_extractor must be set")
-        if wide:
+        if str_pid:
+            # the column becomes its 64-bit hashes: wide privacy ids from here
+            # on.  The invalid-offset count stays on the device until
+            # encode_privacy_ids agrees on the errors of every rank
+            pid_ids, pid_bad_offsets = string_columns.device_keys(
+                *pid.device_columns(device), pid.hash_seed, ctx)
+            pid_unencoded = True
+            wide = True
+        elif wide:
             if pid_range is not None:
                 raise ValueError("wide_privacy_ids=True encodes the privacy ids itself: "
                                  "privacy_id_range must not be given")
@@ -481,7 +561,9 @@ def encode(col, extractors, device: torch.device, need_values: bool,
                        pid_unencoded=pid_unencoded,
                        pid_range_declared=pid_unencoded and pid_range is not None,
                        pk_sparse=bool(sparse), public_keys=sparse_public, pid_wide=bool(wide),
-                       max_distinct_pids=col.max_distinct_privacy_ids if wide else None)
+                       max_distinct_pids=(col.max_distinct_privacy_ids
+                                          if wide and isinstance(col, ColumnarData) else None),
+                       pid_bad_offsets=pid_bad_offsets)
     if pub_range is not None:
         enc.public_mask, enc.public_count = _range_bitmap(*pub_range, int(P), device)
     elif pub_dense is not None:

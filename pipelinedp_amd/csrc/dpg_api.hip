@@ -68,6 +68,7 @@ static hipError_t set_func_attr(const void *kern, hipFuncAttribute attr, int val
 #include "dpg_common.h"
 #include "dpg_hist.h"
 #include "dpg_keydict.h"
+#include "dpg_strkey.h"
 #include "dpg_owner.h"
 #include "dpg_pairx.h"
 #include "dpg_partition.h"
@@ -3214,6 +3215,61 @@ int dpg_keydict_gather_ids(dpg_ctx *ctx, const uint32_t *out_slots, int64_t n,
     k_keydict_gather_ids<<<blocks, kKdThreads, 0, s>>>(
         out_slots, (uint32_t)n, slot_ids, (uint32_t)(capacity - 1), out_ids,
         reinterpret_cast<unsigned long long *>(n_missing));
+    LAUNCH_CHECK();
+    return DPG_OK;
+}
+
+// ---- string columns: keys, slot representatives, verification (dpg_strkey.h)
+int dpg_string_hash(dpg_ctx *ctx, const int64_t *offsets, const uint8_t *data, int64_t data_len,
+                    int64_t n, uint64_t seed, int64_t *out_keys, int64_t *info, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (n < 0 || data_len < 0 || !info || (data_len > 0 && !data) ||
+        (n > 0 && (!offsets || !out_keys)))
+        return fail(ctx, DPG_ERR_INVALID_ARG,
+                    "n < 0, data_len < 0, or offsets, data, out_keys or info is NULL");
+    if (n >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n must be < 2^31 per device");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) return DPG_OK;
+    k_string_hash<<<keydict_blocks(ctx, n), kKdThreads, 0, s>>>(
+        offsets, data, data_len, (uint32_t)n, seed, reinterpret_cast<uint64_t *>(out_keys),
+        reinterpret_cast<unsigned long long *>(info));
+    LAUNCH_CHECK();
+    return DPG_OK;
+}
+
+int dpg_keydict_representatives(dpg_ctx *ctx, const uint32_t *rec_slots, int64_t n,
+                                int64_t capacity, uint32_t *rep, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (!rep) return fail(ctx, DPG_ERR_INVALID_ARG, "rep is NULL");
+    if (const char *e = keydict_table_error(rep, capacity)) return fail(ctx, DPG_ERR_INVALID_ARG, e);
+    if (n < 0 || (n > 0 && !rec_slots))
+        return fail(ctx, DPG_ERR_INVALID_ARG, "n < 0, or rec_slots is NULL");
+    if (n >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n must be < 2^31 per device");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) return DPG_OK;
+    k_keydict_reps<<<keydict_blocks(ctx, n), kKdThreads, 0, s>>>(
+        rec_slots, (uint32_t)n, (uint32_t)(capacity - 1), rep);
+    LAUNCH_CHECK();
+    return DPG_OK;
+}
+
+int dpg_string_verify(dpg_ctx *ctx, const int64_t *offsets, const uint8_t *data, int64_t data_len,
+                      int64_t n, const uint32_t *rec_slots, const uint32_t *rep,
+                      int64_t *n_mismatch, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (n < 0 || data_len < 0 || !n_mismatch || !rep || (data_len > 0 && !data) ||
+        (n > 0 && (!offsets || !rec_slots)))
+        return fail(ctx, DPG_ERR_INVALID_ARG,
+                    "n < 0, data_len < 0, or offsets, data, rec_slots, rep or n_mismatch is NULL");
+    if (n >= 0x80000000ll) return fail(ctx, DPG_ERR_UNSUPPORTED, "n must be < 2^31 per device");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) return DPG_OK;
+    k_string_verify<<<keydict_blocks(ctx, n), kKdThreads, 0, s>>>(
+        offsets, data, data_len, (uint32_t)n, rec_slots, rep,
+        reinterpret_cast<unsigned long long *>(n_mismatch));
     LAUNCH_CHECK();
     return DPG_OK;
 }

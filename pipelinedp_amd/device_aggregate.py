@@ -353,7 +353,8 @@ class DeviceAggregation:
         enc = columnar.encode(self.col, self.extractors, dev, need_values,
                               self.public_partitions,
                               need_pid=not self.bounds_already_enforced, allow_sparse=True,
-                              vector_size=self.plan.vector_size if self.plan is not None else None)
+                              vector_size=self.plan.vector_size if self.plan is not None else None,
+                              ctx=ctx, world_size=backend.world_size)
         if enc.pk_sparse:
             self._encode_sparse_keys(enc)
         if self.bounds_already_enforced:

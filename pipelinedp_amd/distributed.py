@@ -99,6 +99,13 @@ records are in place: `encode_privacy_ids` numbers each rank's distinct ids in
 the same kind of hash table, probed once per record, and adds one all_reduce
 that makes every rank raise the same error.
 
+A StringColumn of privacy ids (string_columns.py) is
+hashed to such wide ids when the input is encoded, so all of the above holds
+for it: the owner of a string is `shard_of_wide(string_key_hash(column), R)`.
+Records with invalid offsets are counted on the device and travel in
+`encode_privacy_ids`' all_reduce, so every rank raises for them together.  A
+StringColumn of partition keys is one-process only.
+
 Every random draw is keyed by (stream seed, pid, pk) or (stream seed, pk)
 with global partition ids -- never by rank -- and the release nonce comes
 from rank 0, so the selected-partition set is identical for any world size
@@ -110,6 +117,8 @@ from typing import Dict, Optional, Tuple
 
 import torch
 import torch.distributed as dist
+
+from . import string_columns
 
 _PACK_ORDER = ("rows", "count", "sum", "nsum", "nsq")
 _PACK_DTYPE = {"rows": torch.int64, "count": torch.int64, "sum": torch.float64,
@@ -131,6 +140,26 @@ def shard_of_wide(pid, world_size: int) -> torch.Tensor:
     (user << 32) to one rank.  Device form: dpg_shard_records_wide,
     dpg_check_shard_wide."""
     return key_owner(pid, world_size)
+
+
+def string_key_hash(column, ctx=None) -> torch.Tensor:
+    """The 64-bit keys (int64 bit patterns) of a StringColumn's records: what
+    a string privacy id becomes, so a caller can pre-shard for "trusted" with
+    shard_of_wide(string_key_hash(column), R).  A column whose tensors are on
+    the device is hashed there (dpg_string_hash, with the library context
+    `ctx` or a temporary one) and the keys stay there; any other column is
+    hashed by the numpy restatement (string_columns.host_keys).  Records with
+    invalid offsets get the key 0; the encoder raises for them."""
+    if column.is_on_device():
+        dev = column.offsets.device
+        if ctx is None:
+            from . import _native
+            ctx = _native.Context(dev.index if dev.index is not None
+                                  else torch.cuda.current_device(), 0)
+        keys, _ = string_columns.device_keys(*column.device_columns(dev), column.hash_seed, ctx)
+        return keys
+    keys, _ = string_columns.host_keys(*column.host_columns(), column.hash_seed)
+    return torch.from_numpy(keys)
 
 
 def owned(P: int, world_size: int, rank: int) -> Tuple[int, int, int]:
@@ -684,7 +713,9 @@ def encode_privacy_ids(enc, backend) -> None:
     precondition failures (n >= 2^31, the table calls' limit); no rank raises
     between `place_records` and this collective, a rank without records runs
     it too, and after it every rank raises the same ValueError.  One process
-    raises directly."""
+    raises directly.  The ids of a StringColumn are its hashes
+    (columnar.encode) and arrive here with the count of records whose offsets
+    were invalid (enc.pid_bad_offsets), which travels in the same all_reduce."""
     if not enc.pid_wide:
         return
     world = backend.world_size
@@ -709,11 +740,15 @@ def encode_privacy_ids(enc, backend) -> None:
         if max_distinct is not None:  # the device table's capacity, mirrored
             n_lost = max(0, D - _pid_capacity(n, max_distinct))
         finish = lambda: inv.to(torch.int64)
+    bad_offsets = int(enc.pid_bad_offsets.item()) if enc.pid_bad_offsets is not None else 0
     if world > 1:
-        t = torch.tensor([n_reserved, n_lost, too_many], dtype=torch.int64,
+        t = torch.tensor([n_reserved, n_lost, too_many, bad_offsets], dtype=torch.int64,
                          device=_coll_device(group, dev))
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-        n_reserved, n_lost, too_many = t.tolist()
+        n_reserved, n_lost, too_many, bad_offsets = t.tolist()
+    if bad_offsets:
+        raise ValueError(f"{bad_offsets} records of the privacy id StringColumn have offsets "
+                         f"outside 0 <= offsets[i] <= offsets[i + 1] <= len(data)")
     if too_many:
         raise ValueError("wide privacy ids: a rank holds 2^31 or more records; the id "
                          "dictionary takes fewer")
@@ -734,6 +769,7 @@ def encode_privacy_ids(enc, backend) -> None:
         enc.pid = finish()
     enc.pid_min, enc.pid_count = 0, max(1, D)
     enc.pid_wide = False
+    enc.pid_bad_offsets = None
 
 
 def exchange_owner_pairs(pairs: torch.Tensor, n_pairs: int, P: int, group, ctx=None,

@@ -28,9 +28,10 @@ from pipelinedp_amd.dataset_histograms import computing_histograms
 
 def _as_collection(public_partitions):
     """Public partitions as a re-iterable collection: ranges, arrays and
-    tensors stay as they are (the device builds their bitmap), anything else
-    (e.g. a generator) is listed."""
-    if isinstance(public_partitions, (range, list, tuple, np.ndarray, torch.Tensor)):
+    tensors stay as they are (the device builds their bitmap), as does a
+    StringColumn; anything else (e.g. a generator) is listed."""
+    if isinstance(public_partitions, (range, list, tuple, np.ndarray, torch.Tensor,
+                                      columnar.StringColumn)):
         return public_partitions
     return list(public_partitions)
 

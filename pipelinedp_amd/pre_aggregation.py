@@ -62,7 +62,8 @@ def device_pairs(col, extractors, backend, public_partitions, dev,
     global partition ids and the global P."""
     enc = columnar.encode(col, extractors, dev,
                           need_values=extractors.value_extractor is not None,
-                          public_partitions=public_partitions)
+                          public_partitions=public_partitions, ctx=backend.ctx,
+                          world_size=backend.world_size)
     P = enc.n_partitions
     ranks = backend.world_size
     if ranks > 1:
