@@ -865,7 +865,11 @@ int dpg_vector_clip_noise(dpg_ctx *ctx, const double *sums, int64_t n_partitions
  * in the environment (a test hook: one more host synchronisation) the
  * zero-length markers "items.regions=window" / "items.regions=lookup" follow
  * "items:scatter": sub-tiles of the first item level whose regions were
- * resolved wave-uniformly / by the per-lane lookup. */
+ * resolved wave-uniformly / by the per-lane lookup.  With
+ * DPG_DEBUG_TEAM_PATHS set (the same kind of hook) the markers
+ * "team.pieces=pair" / "team.pieces=lookup" follow "partition2:team" when
+ * level 2 runs by teams on level-1 pieces: members' shares loaded with one
+ * compare per load / by the 8-piece lookup. */
 int dpg_last_stage_times(dpg_ctx *ctx, char *names, size_t names_len,
                          double *ms, int32_t max_stages, int32_t *n_stages);
 

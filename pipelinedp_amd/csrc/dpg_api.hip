@@ -138,6 +138,9 @@ struct Control {  // device-side counters, zeroed per call
     // sub-tiles of the first item level scattered with their regions resolved
     // uniformly / by the per-lane lookup (SrcSeg; DPG_DEBUG_ITEM_PATHS)
     uint32_t seg_paths[2];
+    // piece-mode team shares loaded by the pair arm / the 8-piece lookup
+    // (dpg_team.h team_resolve; DPG_DEBUG_TEAM_PATHS)
+    uint32_t team_paths[2];
     unsigned long long over_records;
     unsigned long long over2_records;
     unsigned long long pid_lo, pid_hi;  // order-preserving (x ^ 2^63) min / max
@@ -1334,7 +1337,7 @@ __global__ void k_region_base(int64_t *rbase, uint32_t F, uint32_t C) {
 }
 
 // Bucket totals of the pieces and the buckets' starts in the compact level-2
-// output (one workgroup; F <= 2048).
+// output (one workgroup; F <= 4096).
 // desc[d]: the bucket's pieces in one record for the team level 2's scalar
 // loads (dpg_team.h PieceDesc).
 __global__ __launch_bounds__(1024) void k_piece_totals(const uint32_t *cum, const int64_t *rbase,
@@ -1467,7 +1470,9 @@ int run_team_level2(dpg_ctx *ctx, hipStream_t s, const SrcAoS<R> &src, uint32_t 
     WS(tot, uint32_t, "partition2.tot", (size_t)S * F2);
     HIP_TRY(hipMemsetAsync(tw, 0, words * 4, s));
     uint32_t *abort_flag = tw + (size_t)8 * 3 * F + 8 * kTeamArriveStride;
-    const TeamSync ts{tw, tw + (size_t)8 * 3 * F, abort_flag, &ctl->err};
+    TeamSync ts{tw, tw + (size_t)8 * 3 * F, abort_flag, &ctl->err};
+    const bool dbg_paths = pt && std::getenv("DPG_DEBUG_TEAM_PATHS");
+    if (dbg_paths) ts.paths = ctl->team_paths;
     if (std::getenv("DPG_DEBUG_TEAM_ABORT")) {
         // test hook: the team gives up at its first barrier, as after a
         // timeout (abort flag and err bit 8), so the host redoes level 2
@@ -1510,6 +1515,15 @@ int run_team_level2(dpg_ctx *ctx, hipStream_t s, const SrcAoS<R> &src, uint32_t 
             k_part2_team<R, false, true><<<(unsigned)ctx->n_cu, kScatThreads, team_lds<R>(), s>>>(
                 src, seg_start, seg_cnt, S, F2, out, base, tot, ts, PieceTab{}, sub_cap);
         LAUNCH_CHECK();
+    }
+    if (dbg_paths) {
+        // test hook: zero-length stage markers of the arms the members'
+        // piece loads took (a host round trip)
+        uint32_t hp[2];
+        HIP_TRY(hipMemcpyAsync(hp, ctl->team_paths, sizeof(hp), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (hp[0]) stage(ctx, s, "team.pieces=pair");
+        if (hp[1]) stage(ctx, s, "team.pieces=lookup");
     }
     *base_out = base;
     *tot_out = tot;
@@ -2035,6 +2049,26 @@ int dpg_set_seed(dpg_ctx *c, uint64_t seed) {
 }
 
 uint64_t dpg_stream_seed(uint64_t seed, uint64_t nonce) { return stream_seed(seed, nonce); }
+
+// Debug export (tests, no GPU): the team level 2's resolution of a member's
+// share [b0, b0 + max(lim, 2)) to its pieces (dpg_team.h team_resolve) --
+// out = {bnd, dl0, ce0, dl1, ce1, pair}.
+void dpg_debug_team_resolve(const uint32_t *ppre, const uint32_t *dl, const uint32_t *ce, uint32_t b0,
+                            uint32_t lim, uint32_t *out) {
+    uint32_t a[8], b[8], c[8];
+    for (int p = 0; p < 8; ++p) {
+        a[p] = ppre[p];
+        b[p] = dl[p];
+        c[p] = ce[p];
+    }
+    const dpg::PieceSpan r = dpg::team_resolve(a, b, c, b0, lim);
+    out[0] = r.bnd;
+    out[1] = r.dl0;
+    out[2] = r.ce0;
+    out[3] = r.dl1;
+    out[4] = r.ce1;
+    out[5] = r.pair;
+}
 
 int dpg_set_tuning(dpg_ctx *ctx, int32_t bucket_target, int32_t bucket_cap) {
     if (!ctx) return DPG_ERR_INVALID_ARG;

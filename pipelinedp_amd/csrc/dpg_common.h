@@ -382,4 +382,23 @@ __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t x, uint32_t &total) 
     return (uint32_t)v - x;
 }
 
+// Second step of a 1024-thread block scan: sh16 holds the 16 wave totals
+// (written before the caller's barrier).  Returns the sum of the totals of
+// the waves below this one, `total` = all 16.  Every lane reads sh16[lane mod
+// 16] -- one LDS round trip for the wave -- the rows are scanned by DPP, and
+// the wave picks its prefix by its uniform index: no branch, no chain of
+// dependent reads (a loop `if (w < wave) e += sh16[w]` over a per-lane wave
+// index compiled to 15 exec-masked reads, each waited for).
+__device__ __forceinline__ uint32_t block_prefix16(const uint32_t *sh16, uint32_t &total) {
+    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    int v = (int)sh16[threadIdx.x & 15u];
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);  // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);  // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);  // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);  // row_shr:8
+    total = (uint32_t)__builtin_amdgcn_readlane(v, 15);
+    const uint32_t below = (uint32_t)__builtin_amdgcn_readlane(v, (int)(w ? w - 1u : 0u));
+    return w ? below : 0u;
+}
+
 }  // namespace dpg

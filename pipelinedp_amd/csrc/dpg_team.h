@@ -40,6 +40,18 @@ constexpr int kTeamIPT = 16;                       // records per thread
 #ifndef DPG_TEAM_WB
 #define DPG_TEAM_WB 4  // staged records per thread per write-out batch
 #endif
+#ifndef DPG_TEAM_PAIR
+#define DPG_TEAM_PAIR 1  // piece mode: a share's pieces resolved once (team_resolve), one compare per load
+#endif
+#ifndef DPG_TEAM_DESC_AHEAD
+// piece mode: the next bucket's descriptor fetched and resolved a bucket ahead, in front of the
+// arrival at the team barrier, where every member pays for it (same-box A/B, config 2: team stage
+// 4.22 -> 4.49 ms): off, the descriptor is read and resolved after the arrival, in the barrier's shadow
+#define DPG_TEAM_DESC_AHEAD 0
+#endif
+#ifndef DPG_TEAM_SCAN1
+#define DPG_TEAM_SCAN1 1  // block scans: the 16 wave totals in one LDS round trip (block_prefix16)
+#endif
 constexpr uint32_t kTeamF = 2048;                  // digits (11 bits)
 constexpr int kTeamSub = kScatThreads * kTeamIPT;  // records per member per bucket
 constexpr uint64_t kTeamTimeout = 50000000ull;     // wall_clock64 ticks (100 MHz): 0.5 s
@@ -50,6 +62,9 @@ struct TeamSync {
     uint32_t *arrive;  // [8 * kTeamArriveStride] arrivals per team (zeroed)
     uint32_t *abort;   // nonzero: a barrier timed out, every member leaves
     uint32_t *err;     // Control::err; bit 8 = team barrier timeout
+    // test hook (DPG_DEBUG_TEAM_PATHS), else null: piece-mode shares loaded
+    // by the pair arm [0] / the 8-piece lookup [1], added once per workgroup
+    uint32_t *paths = nullptr;
 };
 
 template <class R>
@@ -158,9 +173,148 @@ __device__ __forceinline__ void sload_desc(const PieceDesc *p, u32x16 &a, u32x16
                  : "s"(p)
                  : "memory");
 }
+// The same without a wait of its own: loads from the constant address space
+// (the descriptors are written by an earlier kernel), which the compiler
+// waits for at their first use -- the next bucket's descriptor is fetched at
+// the head of the current bucket and first used after its ranking.
+__device__ __forceinline__ void sload_desc_early(const PieceDesc *p, u32x16 &a, u32x16 &b) {
+    typedef const u32x16 __attribute__((address_space(4))) * ConstVec;
+    const ConstVec q = (ConstVec)(uintptr_t)uniform_ptr(p);
+    a = q[0];
+    b = q[1];
+}
 
-// Level 2 over S level-1 buckets (seg_start / seg_cnt; every count <= T *
-// kTeamSub, checked by the host): records of bucket s land in out[seg_start[s],
+// A member's share [b0, b0 + max(lim, 2)) of a bucket's padded index space,
+// resolved to its pieces once: index i lies in the last piece p with i >=
+// ppre[p] (empty pieces share their successor's ppre and are never chosen
+// before it).  dl0 / ce0 are dl / cend of the piece of the share's first
+// even index b0, dl1 / ce1 those of its last one, bnd = ppre of the latter.
+// pair: no non-empty piece lies between the two, so index i of the share
+// takes (dl1, ce1) if i >= bnd and (dl0, ce0) otherwise -- one compare per
+// load.  With near-equal pieces (one per XCD, n / 8 each) and shares of n /
+// 32 that is every share; tiny buckets and buckets whose records sit in one
+// XCD's tiles span more pieces and take the 8-piece lookup.
+// Plain integer code: runs in scalar registers on the device (every input is
+// wave-uniform) and on the host (dpg_debug_team_resolve, tests).
+struct PieceSpan {
+    uint32_t bnd, dl0, ce0, dl1, ce1, pair;
+};
+__host__ __device__ inline PieceSpan team_resolve(const uint32_t (&ppre)[8], const uint32_t (&dl)[8],
+                                                  const uint32_t (&ce)[8], uint32_t b0, uint32_t lim) {
+    const uint32_t i0 = b0, i1 = b0 + (lim > 2u ? lim : 2u) - 2u;
+    PieceSpan r{ppre[0], dl[0], ce[0], dl[0], ce[0], 0u};
+    // The selections are word masks (all ones: i >= ppre[p]; indices are
+    // below 2^31) and not conditions: uniform conditions live in 64-bit lane
+    // masks on the device, and the seven of a chain, each used by three
+    // selections, were kept (and spilled) as such.
+    const uint32_t n0 = ~i0, n1 = ~i1;
+    uint32_t m0[8], m1[8];
+#pragma unroll
+    for (int p = 1; p < 8; ++p) {
+        m0[p] = (uint32_t)((int32_t)(ppre[p] + n0) >> 31);  // ppre[p] - i0 - 1 < 0
+        m1[p] = (uint32_t)((int32_t)(ppre[p] + n1) >> 31);
+#ifdef __HIP_DEVICE_COMPILE__
+        asm("" : "+s"(m0[p]), "+s"(m1[p]));  // opaque: stays a word in a scalar register
+#endif
+        r.dl0 ^= (r.dl0 ^ dl[p]) & m0[p];
+        r.ce0 ^= (r.ce0 ^ ce[p]) & m0[p];
+        r.dl1 ^= (r.dl1 ^ dl[p]) & m1[p];
+        r.ce1 ^= (r.ce1 ^ ce[p]) & m1[p];
+        r.bnd ^= (r.bnd ^ ppre[p]) & m1[p];
+    }
+    // a non-empty piece p after the first index's (i0 < ppre[p]) and before
+    // the last index's (ppre[p + 1] <= i1) rules the pair arm out
+    uint32_t mid = 0;
+#pragma unroll
+    for (int p = 1; p < 7; ++p)
+        mid |= ~m0[p] & m1[p + 1] & (uint32_t)((int32_t)(ppre[p] - ppre[p + 1]) >> 31);
+    r.pair = ~mid & 1u;
+    return r;
+}
+
+// Piece-mode loads of a share [b0, b0 + lim) (lim >= 2, both even) of a
+// bucket's padded index space, as 16-byte pairs: load mm of a thread reads
+// the pair at even index i = b0 + min(2 kScatThreads mm + 2 tid, lim - 2),
+// whose piece has offset d and ends at c; byte offset boff[mm] from the
+// bucket's first region, bits 2 mm and 2 mm + 1 of the returned mask = the
+// two are records (not padding).  The address step is apart from the loads
+// (team_fetch) so that every path issues the same eight loads back to back
+// and the loads before them (the team barrier's first poll) are waited for
+// by count.
+//
+// From the bucket's PieceDesc in scalar registers: every load looks its
+// piece up in the 8-piece chain.
+__device__ __forceinline__ uint32_t team_addr_lookup(const u32x16 &da, const u32x16 &db, uint32_t b0,
+                                                     uint32_t lim, uint32_t (&boff)[kTeamIPT / 2]) {
+    uint32_t ppre[8], dl[8], ce[8];
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+        ppre[p] = da[6 + p];
+        dl[p] = p < 2 ? da[14 + p] : db[p - 2];
+        ce[p] = db[6 + p];
+    }
+    uint32_t vm = 0;
+#pragma unroll
+    for (int mm = 0; mm < kTeamIPT / 2; ++mm) {
+        const uint32_t o = mm * 2 * kScatThreads + 2 * threadIdx.x;
+        const uint32_t i = b0 + min(o, lim - 2);  // even (b0, lim even)
+        uint32_t d = dl[0], c = ce[0];
+#pragma unroll
+        for (int p = 1; p < 8; ++p) {
+            const bool in = i >= ppre[p];
+            d = in ? dl[p] : d;
+            c = in ? ce[p] : c;
+        }
+        boff[mm] = (i + d) * 8u;
+        vm |= (i < c ? 1u : 0u) << (2 * mm);
+        vm |= (i + 1 < c ? 1u : 0u) << (2 * mm + 1);
+    }
+    return vm;
+}
+// For a share resolved to a pair of pieces (team_resolve, sp.pair): one
+// compare per load selects the piece; the mask bits come from it too.
+__device__ __forceinline__ uint32_t team_addr_pair(const PieceSpan &sp, uint32_t b0, uint32_t lim,
+                                                   uint32_t (&boff)[kTeamIPT / 2]) {
+    uint32_t vm = 0;
+#pragma unroll
+    for (int mm = 0; mm < kTeamIPT / 2; ++mm) {
+        const uint32_t o = mm * 2 * kScatThreads + 2 * threadIdx.x;
+        const uint32_t i = b0 + min(o, lim - 2);  // even (b0, lim even)
+        const bool in = i >= sp.bnd;
+        const uint32_t d = in ? sp.dl1 : sp.dl0, c = in ? sp.ce1 : sp.ce0;
+        boff[mm] = (i + d) * 8u;
+        vm |= (i < c ? 1u : 0u) << (2 * mm);
+        vm |= (i + 1 < c ? 1u : 0u) << (2 * mm + 1);
+    }
+    return vm;
+}
+// The eight loads.  Addresses and mask are complete, in their registers,
+// before the first load: left to the compiler, the mask bits were computed
+// where they are used, after the team barrier, from compare masks kept
+// (spilled to vector lanes) until then.
+template <class R>
+__device__ __forceinline__ void team_fetch(const R *a, int64_t base0, uint32_t (&boff)[kTeamIPT / 2],
+                                           uint32_t &vm, R (&rec)[kTeamIPT]) {
+    static_assert(sizeof(R) == 8 && kTeamIPT == 16, "piece-mode teams read 8-byte records");
+    asm volatile(""
+                 : "+v"(boff[0]), "+v"(boff[1]), "+v"(boff[2]), "+v"(boff[3]), "+v"(boff[4]),
+                   "+v"(boff[5]), "+v"(boff[6]), "+v"(boff[7]), "+v"(vm));
+    const char *bp = reinterpret_cast<const char *>(a + base0);
+#pragma unroll
+    for (int mm = 0; mm < kTeamIPT / 2; ++mm) {
+        R x0, x1;
+        const u64x2 w = *reinterpret_cast<const u64x2 *>(bp + boff[mm]);
+        const uint64_t w0 = w.x, w1 = w.y;
+        __builtin_memcpy(&x0, &w0, sizeof(R));
+        __builtin_memcpy(&x1, &w1, sizeof(R));
+        rec[2 * mm] = x0;
+        rec[2 * mm + 1] = x1;
+    }
+}
+
+// Level 2 over S level-1 buckets (seg_start / seg_cnt; buckets over sub_cap
+// records per member are left to the kMulti launch): records of bucket s land
+// in out[seg_start[s],
 // + seg_cnt[s]) grouped by digit (F2 <= kTeamF digits; the scans run over
 // kTeamF, the digits past F2 count 0); base_out[s][d] / tot_out[s][d] = start
 // and count of fine bucket (s, d), d < F2.  gridDim.x = 8 T workgroups, all
@@ -292,38 +446,26 @@ __global__ __launch_bounds__(kScatThreads) void k_part2_team(SrcAoS<R> src,
     };
     // the same from the bucket's PieceDesc, already in scalar registers
     auto load_pieces_desc = [&](const u32x16 &da, const u32x16 &db, uint32_t b0, uint32_t lim) {
-        const int64_t base0 = (int64_t)(((uint64_t)da[5] << 32) | da[4]);
-        uint32_t ppre[8], dl[8], ce[8];
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            ppre[p] = da[6 + p];
-            dl[p] = p < 2 ? da[14 + p] : db[p - 2];
-            ce[p] = db[6 + p];
+        uint32_t boff[IPT / 2];
+        uint32_t vm = team_addr_lookup(da, db, b0, lim, boff);
+        team_fetch<R>(src.a, (int64_t)(((uint64_t)da[5] << 32) | da[4]), boff, vm, rec);
+        vmask = vm;
+    };
+    // the same from a resolved share (team_resolve): the pair arm, or
+    // (wave-uniform) the descriptor read again for the 8-piece lookup; the
+    // eight loads follow where the arms join
+    auto load_span = [&](const PieceSpan &sp, int64_t base0, const PieceDesc *dp, uint32_t b0,
+                         uint32_t lim) {
+        uint32_t boff[IPT / 2];
+        uint32_t vm;
+        if (sp.pair) {
+            vm = team_addr_pair(sp, b0, lim, boff);
+        } else {
+            u32x16 da, db;
+            sload_desc(dp, da, db);
+            vm = team_addr_lookup(da, db, b0, lim, boff);
         }
-        const char *bp = reinterpret_cast<const char *>(src.a + base0);
-        uint32_t vm = 0;
-#pragma unroll
-        for (int mm = 0; mm < IPT / 2; ++mm) {
-            const uint32_t o = mm * 2 * kScatThreads + 2 * tid;
-            const uint32_t i = b0 + min(o, lim - 2);  // even (b0, lim even)
-            uint32_t d = dl[0], c = ce[0];
-#pragma unroll
-            for (int p = 1; p < 8; ++p) {
-                const bool in = i >= ppre[p];
-                d = in ? dl[p] : d;
-                c = in ? ce[p] : c;
-            }
-            R x0, x1;
-            const uint32_t boff = (i + d) * (uint32_t)sizeof(R);
-            const u64x2 w = *reinterpret_cast<const u64x2 *>(bp + boff);
-            const uint64_t w0 = w.x, w1 = w.y;
-            __builtin_memcpy(&x0, &w0, sizeof(R));
-            __builtin_memcpy(&x1, &w1, sizeof(R));
-            rec[2 * mm] = x0;
-            rec[2 * mm + 1] = x1;
-            vm |= (i < c ? 1u : 0u) << (2 * mm);
-            vm |= (i + 1 < c ? 1u : 0u) << (2 * mm + 1);
-        }
+        team_fetch<R>(src.a, base0, boff, vm, rec);
         vmask = vm;
     };
     uint32_t k = 0;  // buckets done = team barriers passed
@@ -352,21 +494,67 @@ __global__ __launch_bounds__(kScatThreads) void k_part2_team(SrcAoS<R> src,
     int64_t pf_st = 0;
     uint32_t pf_n = 0, pf_b0 = 0, pf_lim = 0;
     constexpr bool use_desc = kPc && kPF;  // the host always builds pt.desc
+    // kPair: the share is resolved to its pieces (scalar code) apart from the
+    // loads; kAhead: the descriptor of the bucket after this one is fetched
+    // at the head of the bucket's iteration and resolved during its ranking,
+    // so that after the arrival at the team barrier only the eight address
+    // computations stand in front of the loads
+    constexpr bool kPair = use_desc && DPG_TEAM_PAIR;
+    constexpr bool kAhead = use_desc && DPG_TEAM_DESC_AHEAD;
+    PieceSpan pf_sp{};
+    int64_t pf_base0 = 0;
+    u32x16 pf_da = {}, pf_db = {};  // !kPair: the descriptor itself is kept
+    uint32_t n_pair = 0, n_lookup = 0;  // shares per arm (ts.paths)
+    // the prefetched share's bounds (and pieces) from its bucket's descriptor
+    auto take_desc = [&](const u32x16 &da, const u32x16 &db) {
+        pf_n = __builtin_amdgcn_readfirstlane(da[0]);
+        pf_st = (int64_t)(((uint64_t)da[3] << 32) | da[2]);
+        const uint32_t q = ((pf_n + T - 1) / T + 1) & ~1u;
+        pf_b0 = min(pf_n, m * q);
+        pf_lim = min(pf_n, pf_b0 + q) - pf_b0;
+        if constexpr (kPair) {
+            uint32_t ppre[8], dl[8], ce[8];
+#pragma unroll
+            for (int p = 0; p < 8; ++p) {
+                ppre[p] = da[6 + p];
+                dl[p] = p < 2 ? da[14 + p] : db[p - 2];
+                ce[p] = db[6 + p];
+            }
+            pf_base0 = (int64_t)(((uint64_t)da[5] << 32) | da[4]);
+            pf_sp = team_resolve(ppre, dl, ce, pf_b0, pf_lim);
+            // computed here, in scalar registers: the compiler otherwise
+            // sinks all of this to its use, behind the arrival at the team
+            // barrier and in front of the loads
+            asm volatile(""
+                         : "+s"(pf_sp.bnd), "+s"(pf_sp.dl0), "+s"(pf_sp.ce0), "+s"(pf_sp.dl1),
+                           "+s"(pf_sp.ce1), "+s"(pf_sp.pair), "+s"(pf_b0), "+s"(pf_lim), "+s"(pf_base0));
+        } else {
+            pf_da = da;
+            pf_db = db;
+        }
+    };
+    // branch-free but for the uniform choice of the arm: past the last bucket
+    // (s >= S) the loads read the last one, a member past the bucket's end
+    // reads its tail (inside the regions, masked out): no path without
+    // loads, so the barrier's first poll is waited for by count
+    auto issue_share = [&](uint32_t s) {
+        if constexpr (kPair) {
+            if (s < S) {
+                n_pair += pf_sp.pair;
+                n_lookup += 1u - pf_sp.pair;
+            }
+            load_span(pf_sp, pf_base0, pt.desc + min(s, S - 1), pf_b0, max(pf_lim, 2u));
+        } else {
+            load_pieces_desc(pf_da, pf_db, pf_b0, max(pf_lim, 2u));
+        }
+    };
     auto load_share = [&](uint32_t s) {
         if constexpr (kPc) {
             if constexpr (use_desc) {
-                // branch-free: past the last bucket (s = S) the loads read the
-                // last one, a member past the bucket's end reads its tail
-                // (inside the regions, masked out): no path without loads,
-                // so the barrier's first poll is waited for by count
                 u32x16 da, db;
                 sload_desc(pt.desc + min(s, S - 1), da, db);
-                pf_n = __builtin_amdgcn_readfirstlane(da[0]);
-                pf_st = (int64_t)(((uint64_t)da[3] << 32) | da[2]);
-                const uint32_t q = ((pf_n + T - 1) / T + 1) & ~1u;
-                pf_b0 = min(pf_n, m * q);
-                pf_lim = min(pf_n, pf_b0 + q) - pf_b0;
-                load_pieces_desc(da, db, pf_b0, max(pf_lim, 2u));
+                take_desc(da, db);
+                issue_share(s);
                 return;
             }
         }
@@ -451,9 +639,14 @@ __global__ __launch_bounds__(kScatThreads) void k_part2_team(SrcAoS<R> src,
             uint32_t e = wave_excl_scan(x, wt);
             if (lane == 63) sh16[wv] = wt;
             __syncthreads();
+#if DPG_TEAM_SCAN1
+            uint32_t all;
+            e += block_prefix16(sh16, all);
+#else
 #pragma unroll
             for (int w = 0; w < kScatThreads / 64; ++w)
                 if (w < wv) e += sh16[w];
+#endif
             uint32_t *tz = ts.tot + ((size_t)team * 3 + (k + 1) % 3) * F;  // the bucket after next
 #pragma unroll
             for (int u = 0; u < DPT; ++u) {
@@ -543,11 +736,15 @@ __global__ __launch_bounds__(kScatThreads) void k_part2_team(SrcAoS<R> src,
                     if (lane == 63) sh16[wv] = wt;
                     __syncthreads();
                     uint32_t nvj = 0;
+#if DPG_TEAM_SCAN1
+                    e += block_prefix16(sh16, nvj);
+#else
 #pragma unroll
                     for (int w = 0; w < kScatThreads / 64; ++w) {
                         if (w < wv) e += sh16[w];
                         nvj += sh16[w];
                     }
+#endif
 #pragma unroll
                     for (int u = 0; u < DPT; ++u) {
                         dstart[d0 + u] = e;
@@ -574,6 +771,10 @@ __global__ __launch_bounds__(kScatThreads) void k_part2_team(SrcAoS<R> src,
         uint32_t *tt = ts.tot + ((size_t)team * 3 + k % 3) * F;
         // ---- load + rank
         if constexpr (!kPF) load_share(s);
+        // the descriptor of the team's next bucket, on its way during the
+        // ranking (used once the reservations below are issued)
+        u32x16 nda = {}, ndb = {};
+        if constexpr (kAhead) sload_desc_early(pt.desc + min(s + 8, S - 1), nda, ndb);
         uint32_t dr[IPT];
         uint32_t nv = 0;  // records of the share (lim less the padding)
         {
@@ -609,15 +810,36 @@ __global__ __launch_bounds__(kScatThreads) void k_part2_team(SrcAoS<R> src,
             uint32_t o[DPT];
 #pragma unroll
             for (int u = 0; u < DPT; ++u) o[u] = atomicAdd(&tt[d0 + u], c[u]);
+            if constexpr (kAhead) {
+                // the next non-empty bucket and this member's share of it,
+                // resolved in scalar code while the reservations are under
+                // way: almost always the team's next bucket, whose descriptor
+                // has arrived; else (uniform) the search and a second fetch
+                uint32_t ns = s + 8;
+                const uint32_t nn = __builtin_amdgcn_readfirstlane(nda[0]);
+                if (ns < S && (nn == 0 || share_q(nn) > sub_cap)) {
+                    ns = next_nonempty(ns + 8);
+                    u32x16 da, db;
+                    sload_desc(pt.desc + min(ns, S - 1), da, db);
+                    take_desc(da, db);
+                } else {
+                    take_desc(nda, ndb);
+                }
+                pf_s = ns;
+            }
             uint32_t wt;
             uint32_t e = wave_excl_scan(x, wt);
             if (lane == 63) sh16[wv] = wt;
             __syncthreads();
+#if DPG_TEAM_SCAN1
+            e += block_prefix16(sh16, nv);
+#else
 #pragma unroll
             for (int w = 0; w < kScatThreads / 64; ++w) {
                 if (w < wv) e += sh16[w];
                 nv += sh16[w];
             }
+#endif
 #pragma unroll
             for (int u = 0; u < DPT; ++u) {
                 dstart[d0 + u] = e;
@@ -637,12 +859,14 @@ __global__ __launch_bounds__(kScatThreads) void k_part2_team(SrcAoS<R> src,
                 }
 #pragma unroll
                 for (int u = 0; u < DPT; ++u) cur[d0 + u] = o[u];
-                pf_s = next_nonempty(s + 8);
+                if constexpr (!kAhead) pf_s = next_nonempty(s + 8);
             }
         }
         ++k;
         auto prefetch = [&]() {
-            if constexpr (kPF) {
+            if constexpr (kAhead) {
+                issue_share(pf_s);
+            } else if constexpr (kPF) {
                 if (use_desc || pf_s < S) load_share(pf_s);
             }
         };
@@ -662,9 +886,14 @@ __global__ __launch_bounds__(kScatThreads) void k_part2_team(SrcAoS<R> src,
             uint32_t e = wave_excl_scan(x, wt);
             if (lane == 63) sh16[wv] = wt;
             __syncthreads();
+#if DPG_TEAM_SCAN1
+            uint32_t all;
+            e += block_prefix16(sh16, all);
+#else
 #pragma unroll
             for (int w = 0; w < kScatThreads / 64; ++w)
                 if (w < wv) e += sh16[w];
+#endif
             uint32_t *tz = ts.tot + ((size_t)team * 3 + (k + 1) % 3) * F;  // the bucket after next
 #pragma unroll
             for (int u = 0; u < DPT; ++u) {
@@ -714,6 +943,12 @@ __global__ __launch_bounds__(kScatThreads) void k_part2_team(SrcAoS<R> src,
         }
         __syncthreads();  // dstart / cur / stage are rewritten by the next bucket
         }  // !kMulti
+    }
+    if constexpr (kPair) {
+        if (ts.paths && tid == 0) {
+            atomicAdd(&ts.paths[0], n_pair);
+            atomicAdd(&ts.paths[1], n_lookup);
+        }
     }
 }
 
