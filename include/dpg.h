@@ -689,6 +689,54 @@ int dpg_string_verify(dpg_ctx *ctx, const int64_t *offsets, const uint8_t *data,
                       int64_t n, const uint32_t *rec_slots, const uint32_t *rep,
                       int64_t *n_mismatch, void *stream);
 
+/* ---- string columns: gathered into a packed column, runs of equal keys ----
+ * What the global string dictionary (distributed.build_string_dictionary;
+ * csrc/dpg_strpack.h) needs beyond the calls above:
+ * chosen records of a column packed back to back -- the lengths, a prefix sum
+ * by the caller, the bytes -- and, at the owner of a key, the check that every
+ * run of equal keys holds one string.
+ *
+ * All three follow the contract of the string calls above: every count < 2^31
+ * (else DPG_ERR_UNSUPPORTED); m == 0 is a no-op (the per-element pointers may
+ * then be NULL); a negative count or a NULL pointer (data may be NULL when
+ * data_len == 0, out_data when out_total == 0): DPG_ERR_INVALID_ARG; both
+ * before any device work.  The counters are added to, so the caller zeroes
+ * them.  Stream-ordered, no host synchronisation.  The column is offsets
+ * (device int64[n + 1]) and data (device uint8[data_len]) as above; records
+ * (device int64[m]) may repeat and come in any order.
+ *
+ * out_len[j] (device int64[m]) = the byte length of record records[j].  A
+ * records[j] outside [0, n), or offsets that are not 0 <= offsets[r] <=
+ * offsets[r + 1] <= data_len, gives length 0 and adds 1 to info[0] (device
+ * int64[1]). */
+int dpg_string_lengths(dpg_ctx *ctx, const int64_t *offsets, int64_t data_len, int64_t n,
+                       const int64_t *records, int64_t m, int64_t *out_len, int64_t *info,
+                       void *stream);
+/* out_data[out_offsets[j], out_offsets[j + 1]) (out_offsets: device
+ * int64[m + 1]; out_data: device uint8[out_total], not overlapping data)
+ * receives the bytes of record records[j].  A j whose record or offsets are
+ * invalid as above, whose out range is not 0 <= out_offsets[j] <=
+ * out_offsets[j + 1] <= out_total, or whose out range is not as long as the
+ * record writes nothing and adds 1 to info[0] (device int64[1]).  No byte
+ * outside data[0, data_len) is read and none outside the j's own out range is
+ * written, whatever the alignment of data and of out_data. */
+int dpg_string_pack(dpg_ctx *ctx, const int64_t *offsets, const uint8_t *data, int64_t data_len,
+                    int64_t n, const int64_t *records, int64_t m, const int64_t *out_offsets,
+                    uint8_t *out_data, int64_t out_total, int64_t *info, void *stream);
+/* keys (device int64[m]) with equal keys adjacent; order (device uint32[m], or
+ * NULL = the identity): entry j stands for string order[j] of a column of
+ * n_strings strings.  head[j] (device uint8[m]) = 1 if j == 0 or keys[j] !=
+ * keys[j - 1], else 0.  An entry with head[j] == 0 is compared with the entry
+ * before it, string order[j] with string order[j - 1], length first and then
+ * content: a difference adds 1 to info[0] (device int64[2]).  An index outside
+ * [0, n_strings) or invalid offsets on either side read nothing, count as a
+ * difference (info[0] += 1) and add 1 to info[1].  With info[0] == 0 every run
+ * of equal keys holds byte-equal strings. */
+int dpg_string_verify_runs(dpg_ctx *ctx, const int64_t *keys, const uint32_t *order,
+                           const int64_t *offsets, const uint8_t *data, int64_t data_len,
+                           int64_t n_strings, int64_t m, uint8_t *head, int64_t *info,
+                           void *stream);
+
 /* ---- multi-GPU utility analysis: pairs to the rank that owns their partition ----
  * The per-partition utility combiners need every (privacy id, partition) pair
  * of a partition on one rank, so each rank's pre-aggregate travels to the

@@ -31,7 +31,8 @@ EXPORTED = ("dpg_ctx_create", "dpg_ctx_destroy", "dpg_last_error", "dpg_set_seed
             "dpg_keydict_insert", "dpg_keydict_keys", "dpg_keydict_assign",
             "dpg_keydict_lookup", "dpg_keydict_insert_slots", "dpg_keydict_gather_ids",
             "dpg_shard_records_wide", "dpg_check_shard_wide",
-            "dpg_string_hash", "dpg_keydict_representatives", "dpg_string_verify")
+            "dpg_string_hash", "dpg_keydict_representatives", "dpg_string_verify",
+            "dpg_string_lengths", "dpg_string_pack", "dpg_string_verify_runs")
 
 KEYDICT_EMPTY = 1 << 63  # DPG_KEYDICT_EMPTY: the bit pattern of INT64_MIN, the reserved key
 KEYDICT_NO_SLOT = 0xFFFFFFFF  # dpg_keydict_insert_slots: a reserved or lost record
@@ -301,6 +302,12 @@ def load():
         lib.dpg_keydict_representatives.restype = ctypes.c_int
         lib.dpg_string_verify.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, vp]
         lib.dpg_string_verify.restype = ctypes.c_int
+        lib.dpg_string_lengths.argtypes = [vp, vp, i64, i64, vp, i64, vp, vp, vp]
+        lib.dpg_string_lengths.restype = ctypes.c_int
+        lib.dpg_string_pack.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, vp, i64, vp, vp]
+        lib.dpg_string_pack.restype = ctypes.c_int
+        lib.dpg_string_verify_runs.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp]
+        lib.dpg_string_verify_runs.restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -668,6 +675,36 @@ class Context:
         st = self.lib.dpg_string_verify(self.handle, offsets_ptr, data_ptr, int(data_len), int(n),
                                         rec_slots_ptr, rep_ptr, n_mismatch_ptr, stream)
         self.check(st, "dpg_string_verify")
+
+    def string_lengths(self, offsets_ptr, data_len, n, records_ptr, m, out_len_ptr, info_ptr,
+                       stream):
+        """out_len[j] (device int64[m]) = the byte length of record records[j]
+        of an n-record column; an invalid record or invalid offsets give 0 and
+        the device int64 at info_ptr += 1."""
+        st = self.lib.dpg_string_lengths(self.handle, offsets_ptr, int(data_len), int(n),
+                                         records_ptr, int(m), out_len_ptr, info_ptr, stream)
+        self.check(st, "dpg_string_lengths")
+
+    def string_pack(self, offsets_ptr, data_ptr, data_len, n, records_ptr, m, out_offsets_ptr,
+                    out_data_ptr, out_total, info_ptr, stream):
+        """out_data[out_offsets[j]:out_offsets[j + 1]] = the bytes of record
+        records[j]; a j that is invalid or whose out range does not fit writes
+        nothing and the device int64 at info_ptr += 1."""
+        st = self.lib.dpg_string_pack(self.handle, offsets_ptr, data_ptr, int(data_len), int(n),
+                                      records_ptr, int(m), out_offsets_ptr, out_data_ptr,
+                                      int(out_total), info_ptr, stream)
+        self.check(st, "dpg_string_pack")
+
+    def string_verify_runs(self, keys_ptr, order_ptr, offsets_ptr, data_ptr, data_len, n_strings,
+                           m, head_ptr, info_ptr, stream):
+        """head[j] (device uint8[m]) = keys[j] starts a run of equal keys; any
+        other entry's string order[j] (order_ptr None: j) is compared with its
+        predecessor's: info (device int64[2]) += (differences, of which
+        invalid indices or offsets)."""
+        st = self.lib.dpg_string_verify_runs(self.handle, keys_ptr, order_ptr, offsets_ptr,
+                                             data_ptr, int(data_len), int(n_strings), int(m),
+                                             head_ptr, info_ptr, stream)
+        self.check(st, "dpg_string_verify_runs")
 
     def stage_times(self):
         names = ctypes.create_string_buffer(4096)

@@ -110,7 +110,31 @@ class ColumnarData:
     ids -- the hashes -- with everything said above about them, on one rank or
     several; a caller who pre-shards for "trusted" uses
     distributed.shard_of_wide(distributed.string_key_hash(column), R).
-    `privacy_id_range` must not be given (ValueError)."""
+    `privacy_id_range` must not be given (ValueError).
+
+    `global_string_keys` (opt-in): a string `pk` gets its ids from a global
+    string dictionary (distributed.build_string_dictionary; DESIGN.md section
+    19), on one rank or several, under every `sharding` mode and with integer,
+    wide or string privacy ids.  Every rank hashes and verifies its own
+    strings as above; the distinct hashes get global ids i * R + owner from
+    the key dictionary of `sparse_partition_keys`; one representative string
+    per hash travels to the hash's owner, which compares the strings that
+    arrive under one hash -- so two different strings with one hash on
+    DIFFERENT ranks raise the same ValueError on every rank -- and keeps its
+    slice of the string table on the device.  With several ranks that is ten
+    collectives before the records are placed.  Only the strings of the KEPT
+    partitions are decoded on the host; results carry `str` keys, after a
+    gather the same list on every rank.  The ids are the ascending rank of the
+    hashes, not of the sorted strings as without the flag, so under binding
+    bounds or with noise a flagged release draws other samples than the
+    unflagged release of the same data (both are correct releases).  `pk` must
+    be a StringColumn (ValueError otherwise); `n_partitions` and
+    `sparse_partition_keys` stay excluded; `max_distinct_partition_keys` sizes
+    the local table; the public partitions are a list or tuple of `str` or a
+    StringColumn, the same on every rank.  Supported: aggregate with COUNT,
+    SUM, PRIVACY_ID_COUNT, MEAN and VARIANCE, and select_partitions;
+    PERCENTILE, VECTOR_SUM and the analysis, histogram and tune entry points
+    raise NotImplementedError."""
     pid: Any = None
     pk: Any = None
     value: Any = None
@@ -122,8 +146,12 @@ class ColumnarData:
     max_distinct_partition_keys: Optional[int] = None
     wide_privacy_ids: bool = False
     max_distinct_privacy_ids: Optional[int] = None
+    global_string_keys: bool = False
 
     def __post_init__(self):
+        if self.global_string_keys and not isinstance(self.pk, StringColumn):
+            raise ValueError("global_string_keys=True builds a global string dictionary: pk "
+                             "must be a StringColumn")
         if self.sharding not in SHARDING_MODES:
             raise ValueError(f"sharding must be one of {SHARDING_MODES}, got {self.sharding!r}")
         if self.sparse_partition_keys and self.n_partitions is not None:
@@ -180,6 +208,9 @@ class EncodedInput:
     # device int64[1] the records whose offsets were invalid, which
     # distributed.encode_privacy_ids raises for on every rank alike
     pid_bad_offsets: Optional[torch.Tensor] = None
+    # global_string_keys: the distributed.StringDictionary whose ids pk holds
+    # (this rank's slice of the string table; the results' keys come from it)
+    string_dictionary: Any = None
 
 
 def _extract(col, extractor):
@@ -361,10 +392,12 @@ def _range(t: torch.Tensor):
 def encode(col, extractors, device: torch.device, need_values: bool,
            public_partitions=None, need_pid: bool = True,
            allow_sparse: bool = False, vector_size: Optional[int] = None,
-           ctx=None, world_size: int = 1) -> EncodedInput:
+           ctx=None, world_size: int = 1, group=None) -> EncodedInput:
     """`ctx`: the library context of the backend, which a StringColumn needs
     (NotImplementedError without); `world_size`: the backend's, since a string
-    `pk` runs in one process only.  Every returned column is contiguous (a copy only when the caller's is
+    `pk` runs in one process only unless ColumnarData(global_string_keys=True)
+    asks for the global string dictionary, which is then built here over the
+    process group `group` (None: one process).  Every returned column is contiguous (a copy only when the caller's is
     not), int64 / float64, on `device`, and n elements long: the kernels take
     raw pointers.  `vector_size`: None for scalar metrics, whose value column
     is [n] (or [n, 1], flattened; another shape raises ValueError); with
@@ -400,6 +433,15 @@ def encode(col, extractors, device: torch.device, need_values: bool,
     # rank raises alike, before any device work or collective)
     str_pk = isinstance(pk, StringColumn)
     str_pid = need_pid and isinstance(pid, StringColumn)
+    global_str = isinstance(col, ColumnarData) and col.global_string_keys
+    if global_str:
+        if not str_pk:
+            raise ValueError("global_string_keys=True builds a global string dictionary: pk "
+                             "must be a StringColumn")
+        if not allow_sparse:  # the analysis, histogram and tune entry points
+            raise NotImplementedError(
+                "global_string_keys=True is supported by DPEngine.aggregate (COUNT, SUM, "
+                "PRIVACY_ID_COUNT, MEAN, VARIANCE) and select_partitions only")
     if str_pk or str_pid:
         _check_string_columns(pid if str_pid else None, pk, hint,
                               isinstance(col, ColumnarData) and col.sparse_partition_keys,
@@ -407,7 +449,7 @@ def encode(col, extractors, device: torch.device, need_values: bool,
         if ctx is None:
             raise NotImplementedError("a StringColumn is encoded on the device: this entry "
                                       "point does not pass the library context to the encoder")
-    if str_pk and world_size > 1:
+    if str_pk and world_size > 1 and not global_str:
         raise NotImplementedError(
             "a StringColumn of partition keys is supported in one process only: a global "
             "string dictionary across ranks is not built.  Encode the partition keys to dense "
@@ -455,7 +497,17 @@ def encode(col, extractors, device: torch.device, need_values: bool,
     # built over those ids, so they must not be re-encoded
     np_row_keys = (hint is None and not sparse and isinstance(pk, list)
                    and any(isinstance(k, np.generic) for k in pk))
-    if str_pk:
+    string_dictionary = None
+    if global_str:
+        # hashed and verified on the device, ids from the hashes, the strings
+        # checked and kept by their hashes' owners; none reaches the host here
+        string_dictionary = string_columns.encode_global_partition_keys(
+            pk, string_columns.public_strings(public_partitions), device, ctx,
+            col.max_distinct_partition_keys, group)
+        pk_ids, P = string_dictionary.ids, string_dictionary.n_partitions
+        if string_dictionary.public_ids is not None:
+            public_ids = string_dictionary.public_ids.cpu().numpy()
+    elif str_pk:
         # hashed, verified and dictionary-encoded on the device; only the
         # distinct strings reach the host
         pk_ids, key_table, public_ids = string_columns.encode_partition_keys(
@@ -557,13 +609,13 @@ def encode(col, extractors, device: torch.device, need_values: bool,
     enc = EncodedInput(pid=pid_ids, pk=pk_ids.contiguous(), value=val, n=n,
                        n_partitions=int(P), key_table=key_table, pid_min=pid_min,
                        pid_count=pid_count, rec_id_offset=rec_off,
-                       partitions_declared=hint is not None and key_table is None,
+                       partitions_declared=(hint is not None and key_table is None) or global_str,
                        pid_unencoded=pid_unencoded,
                        pid_range_declared=pid_unencoded and pid_range is not None,
                        pk_sparse=bool(sparse), public_keys=sparse_public, pid_wide=bool(wide),
                        max_distinct_pids=(col.max_distinct_privacy_ids
                                           if wide and isinstance(col, ColumnarData) else None),
-                       pid_bad_offsets=pid_bad_offsets)
+                       pid_bad_offsets=pid_bad_offsets, string_dictionary=string_dictionary)
     if pub_range is not None:
         enc.public_mask, enc.public_count = _range_bitmap(*pub_range, int(P), device)
     elif pub_dense is not None:

@@ -69,6 +69,7 @@ static hipError_t set_func_attr(const void *kern, hipFuncAttribute attr, int val
 #include "dpg_hist.h"
 #include "dpg_keydict.h"
 #include "dpg_strkey.h"
+#include "dpg_strpack.h"
 #include "dpg_owner.h"
 #include "dpg_pairx.h"
 #include "dpg_partition.h"
@@ -3304,6 +3305,69 @@ int dpg_string_verify(dpg_ctx *ctx, const int64_t *offsets, const uint8_t *data,
     k_string_verify<<<keydict_blocks(ctx, n), kKdThreads, 0, s>>>(
         offsets, data, data_len, (uint32_t)n, rec_slots, rep,
         reinterpret_cast<unsigned long long *>(n_mismatch));
+    LAUNCH_CHECK();
+    return DPG_OK;
+}
+
+// ---- string columns: lengths, packing, runs of equal keys (dpg_strpack.h)
+int dpg_string_lengths(dpg_ctx *ctx, const int64_t *offsets, int64_t data_len, int64_t n,
+                       const int64_t *records, int64_t m, int64_t *out_len, int64_t *info,
+                       void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (n < 0 || m < 0 || data_len < 0 || !info || (m > 0 && (!offsets || !records || !out_len)))
+        return fail(ctx, DPG_ERR_INVALID_ARG,
+                    "n < 0, m < 0, data_len < 0, or offsets, records, out_len or info is NULL");
+    if (n >= 0x80000000ll || m >= 0x80000000ll)
+        return fail(ctx, DPG_ERR_UNSUPPORTED, "n and m must be < 2^31 per device");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (m == 0) return DPG_OK;
+    k_string_lengths<<<keydict_blocks(ctx, m), kKdThreads, 0, s>>>(
+        offsets, data_len, n, records, (uint32_t)m, out_len,
+        reinterpret_cast<unsigned long long *>(info));
+    LAUNCH_CHECK();
+    return DPG_OK;
+}
+
+int dpg_string_pack(dpg_ctx *ctx, const int64_t *offsets, const uint8_t *data, int64_t data_len,
+                    int64_t n, const int64_t *records, int64_t m, const int64_t *out_offsets,
+                    uint8_t *out_data, int64_t out_total, int64_t *info, void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (n < 0 || m < 0 || data_len < 0 || out_total < 0 || !info || (data_len > 0 && !data) ||
+        (out_total > 0 && !out_data) || (m > 0 && (!offsets || !records || !out_offsets)))
+        return fail(ctx, DPG_ERR_INVALID_ARG,
+                    "n < 0, m < 0, data_len < 0, out_total < 0, or offsets, data, records, "
+                    "out_offsets, out_data or info is NULL");
+    if (n >= 0x80000000ll || m >= 0x80000000ll)
+        return fail(ctx, DPG_ERR_UNSUPPORTED, "n and m must be < 2^31 per device");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (m == 0) return DPG_OK;
+    k_string_pack<<<keydict_blocks(ctx, m), kKdThreads, 0, s>>>(
+        offsets, data, data_len, n, records, (uint32_t)m, out_offsets, out_data, out_total,
+        reinterpret_cast<unsigned long long *>(info));
+    LAUNCH_CHECK();
+    return DPG_OK;
+}
+
+int dpg_string_verify_runs(dpg_ctx *ctx, const int64_t *keys, const uint32_t *order,
+                           const int64_t *offsets, const uint8_t *data, int64_t data_len,
+                           int64_t n_strings, int64_t m, uint8_t *head, int64_t *info,
+                           void *stream) {
+    if (!ctx) return DPG_ERR_INVALID_ARG;
+    if (n_strings < 0 || m < 0 || data_len < 0 || !info || (data_len > 0 && !data) ||
+        (m > 0 && (!keys || !offsets || !head)))
+        return fail(ctx, DPG_ERR_INVALID_ARG,
+                    "n_strings < 0, m < 0, data_len < 0, or keys, offsets, data, head or info "
+                    "is NULL");
+    if (n_strings >= 0x80000000ll || m >= 0x80000000ll)
+        return fail(ctx, DPG_ERR_UNSUPPORTED, "n_strings and m must be < 2^31 per device");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, DPG_ERR_HIP, "hipSetDevice");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (m == 0) return DPG_OK;
+    k_string_verify_runs<<<keydict_blocks(ctx, m), kKdThreads, 0, s>>>(
+        reinterpret_cast<const uint64_t *>(keys), order, offsets, data, data_len, n_strings,
+        (uint32_t)m, head, reinterpret_cast<unsigned long long *>(info));
     LAUNCH_CHECK();
     return DPG_OK;
 }

@@ -36,6 +36,7 @@ from pipelinedp_amd import columnar
 from pipelinedp_amd import combiners
 from pipelinedp_amd import distributed
 from pipelinedp_amd import partition_selection
+from pipelinedp_amd import string_columns
 
 
 # experiments: DPG_SYNC_COMPACT=1 synchronises at the compaction, as before
@@ -82,8 +83,15 @@ class DeviceResult:
 
     def __init__(self, partition_ids: torch.Tensor, values: torch.Tensor, fields: tuple,
                  key_table: Optional[Sequence], stage_ms: Optional[dict] = None,
-                 pending: Optional[tuple] = None, key_map: Optional[torch.Tensor] = None):
+                 pending: Optional[tuple] = None, key_map: Optional[torch.Tensor] = None,
+                 string_dictionary=None, strings: Optional[list] = None):
         self._ids, self._vals = partition_ids, values
+        # global_string_keys: the kept local ids also index the owner's string
+        # table, from which keys() packs and decodes the kept strings -- or
+        # `strings` holds them already (gathered from every rank)
+        self._string_dictionary = string_dictionary
+        self._strings = strings
+        self._local_ids = None
         # sparse partition keys: the kept local ids index this int64 tensor of
         # the caller's keys (the rank's owned keys) instead of being re-based
         self._key_map = key_map
@@ -108,6 +116,8 @@ class DeviceResult:
             raise _native.NativeError(
                 "dpg_compact_kept failed (HIP error): internal hash-table error in bounding")
         ids = self._ids[:k]
+        if self._string_dictionary is not None:
+            self._local_ids = ids.clone()
         if self._key_map is not None:
             ids = self._key_map[ids]
         elif stride != 1 or offset:  # several ranks: this rank's slice
@@ -137,7 +147,20 @@ class DeviceResult:
         self._resolve()
         return self._vals
 
+    def packed_strings(self):
+        """global_string_keys: (offsets int64[K + 1], bytes uint8) of this
+        rank's kept partitions' strings, packed on the device from the owner's
+        string table (dpg_string_pack)."""
+        self._resolve()
+        return self._string_dictionary.packed(self._local_ids)
+
     def keys(self) -> list:
+        if self._strings is None and self._string_dictionary is not None:
+            # only the kept partitions' strings are ever decoded
+            self._strings = string_columns.decode_packed(*self.packed_strings(),
+                                                         self._string_dictionary.encoding)
+        if self._strings is not None:
+            return list(self._strings)
         return columnar.decode_keys(self.partition_ids.cpu().numpy(), self.key_table)
 
 
@@ -179,6 +202,9 @@ class DeviceAggregation:
         self.last_select_fields: Optional[dict] = None
         # sparse_partition_keys: the distributed.KeyDictionary of the release
         self.last_key_dictionary = None
+        # global_string_keys: the distributed.StringDictionary of the release
+        # (the records' ids, P, and this rank's slice of the string table)
+        self.last_string_dictionary = None
 
     # ------------------------------------------------------------ public
     def __iter__(self):
@@ -350,11 +376,21 @@ class DeviceAggregation:
                 "sparse_partition_keys=True supports COUNT, SUM, PRIVACY_ID_COUNT, MEAN and "
                 "VARIANCE; PERCENTILE and VECTOR_SUM need dense partition ids "
                 "(ColumnarData(n_partitions=P))")
+        strkeys = isinstance(self.col, columnar.ColumnarData) and self.col.global_string_keys
+        if strkeys and self.plan is not None and (self.plan.percentiles
+                                                   or self.plan.vector_size is not None):
+            # host state only: every rank raises alike, before any collective
+            raise NotImplementedError(
+                "global_string_keys=True supports COUNT, SUM, PRIVACY_ID_COUNT, MEAN and "
+                "VARIANCE; PERCENTILE and VECTOR_SUM need the one-process string route or dense "
+                "partition ids (ColumnarData(n_partitions=P))")
         enc = columnar.encode(self.col, self.extractors, dev, need_values,
                               self.public_partitions,
                               need_pid=not self.bounds_already_enforced, allow_sparse=True,
                               vector_size=self.plan.vector_size if self.plan is not None else None,
-                              ctx=ctx, world_size=backend.world_size)
+                              ctx=ctx, world_size=backend.world_size,
+                              group=backend.process_group if backend.world_size > 1 else None)
+        self.last_string_dictionary = enc.string_dictionary
         if enc.pk_sparse:
             self._encode_sparse_keys(enc)
         if self.bounds_already_enforced:
@@ -523,7 +559,10 @@ class DeviceAggregation:
             done.record(stream)
             # sparse partition keys: the owner turns its kept local ids into the
             # caller's keys (its slice of the dictionary; no global key table)
-            kd = self.last_key_dictionary if sparse else None
+            # global string keys: the same with the owned hashes, and the owned
+            # string table behind them for keys()
+            sd = self.last_string_dictionary
+            kd = self.last_key_dictionary if sparse else sd
             key_map = None
             if kd is not None:
                 # local_P entries: the ids past this owner's keys are holes,
@@ -532,10 +571,16 @@ class DeviceAggregation:
                 key_map[:kd.owned_keys.numel()] = kd.owned_keys
             res = DeviceResult(ids, kept_out, fields, enc.key_table, stage_ms,
                                pending=(info, n_out, pk_stride, pk_offset, done),
-                               key_map=key_map)
+                               key_map=key_map, string_dictionary=sd)
             if backend.world_size > 1 and gather:
-                ids, vals = distributed.all_gather_results(res.partition_ids, res.values,
-                                                           backend.process_group,
-                                                           exact_ids=kd is not None)
-                res = DeviceResult(ids, vals, fields, enc.key_table, stage_ms)
+                ids, vals, sizes = distributed.all_gather_results(
+                    res.partition_ids, res.values, backend.process_group,
+                    exact_ids=kd is not None, return_sizes=True)
+                strings = None
+                if sd is not None:
+                    # the kept strings follow in the same rank order: two more
+                    # all_gathers, lengths and bytes
+                    strings = distributed.all_gather_strings(
+                        *res.packed_strings(), sizes, backend.process_group, sd.encoding)
+                res = DeviceResult(ids, vals, fields, enc.key_table, stage_ms, strings=strings)
         return res

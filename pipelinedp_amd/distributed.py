@@ -104,7 +104,11 @@ hashed to such wide ids when the input is encoded, so all of the above holds
 for it: the owner of a string is `shard_of_wide(string_key_hash(column), R)`.
 Records with invalid offsets are counted on the device and travel in
 `encode_privacy_ids`' all_reduce, so every rank raises for them together.  A
-StringColumn of partition keys is one-process only.
+StringColumn of partition keys is one-process only unless
+ColumnarData(global_string_keys=True) asks for `build_string_dictionary`: ids
+from the hashes through `build_key_dictionary`, one representative string per
+hash sent to the hash's owner, which verifies the strings arriving under one
+hash and keeps its slice of the string table.
 
 Every random draw is keyed by (stream seed, pid, pk) or (stream seed, pk)
 with global partition ids -- never by rank -- and the release nonce comes
@@ -113,8 +117,9 @@ from rank 0, so the selected-partition set is identical for any world size
 """
 import ctypes
 import dataclasses
-from typing import Dict, Optional, Tuple
+from typing import Any, Dict, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -578,6 +583,269 @@ def build_key_dictionary(pk: torch.Tensor, public_keys: Optional[torch.Tensor], 
         raise RuntimeError(f"key dictionary: {missing} keys have no id (internal error)")
     return KeyDictionary(ids=ids, public_ids=public_ids, n_partitions=P, owned_keys=owned_keys,
                          keys=distinct, key_ids=key_ids)
+
+
+@dataclasses.dataclass
+class StringDictionary:
+    """What build_string_dictionary returns (see there)."""
+    ids: torch.Tensor                    # int64: the global dense id of every record
+    public_ids: Optional[torch.Tensor]   # the same for the public strings, or None
+    n_partitions: int                    # P, the same on every rank
+    owned_keys: torch.Tensor             # this rank's owned hashes, int64, ascending
+    owned_offsets: torch.Tensor          # int64[n_owned + 1]: the owned string table,
+    owned_data: torch.Tensor             # uint8, in owned_keys order
+    encoding: str = "utf-8"
+    ctx: Any = None                      # the library context the table is packed with
+
+    def packed(self, local_ids: torch.Tensor):
+        """(offsets int64[k + 1], bytes uint8) of the owned strings at the
+        given local ids (global id // R), packed on the table's device
+        (string_columns.pack_strings)."""
+        out_offsets, out_data, bad = string_columns.pack_strings(
+            self.owned_offsets, self.owned_data,
+            local_ids.to(torch.int64).to(self.owned_offsets.device), self.ctx)
+        if int(bad.item()):
+            raise RuntimeError(f"string dictionary: {int(bad.item())} kept ids have no owned "
+                               f"string (internal error)")
+        return out_offsets, out_data
+
+    def strings(self, local_ids: torch.Tensor) -> list:
+        """The owned strings at the given local ids, decoded on the host."""
+        return string_columns.decode_packed(*self.packed(local_ids), self.encoding)
+
+
+STRING_OFFSETS_ERROR = ("{} records of the partition key StringColumn have offsets "
+                        "outside 0 <= offsets[i] <= offsets[i + 1] <= len(data)")
+STRING_OVERFLOW_ERROR = (
+    "string partition keys: the key table sized by max_distinct_partition_keys="
+    "{} overflowed ({} records found no slot); raise "
+    "max_distinct_partition_keys to at least the number of distinct partition keys")
+STRING_COLLISION_ERROR = ("{} records or strings share a 64-bit hash with a different string; "
+                          "pass another hash_seed")
+
+
+def _local_string_keys(column, dev, ctx, sptr, max_distinct):
+    """Step 1 of build_string_dictionary on this rank: returns (offsets, data,
+    hashes int64[D] of the distinct strings, their representative records
+    int64[D], finish, [invalid offsets, lost, local mismatches]); finish(ids
+    int64[D]) gives every record the id of its string."""
+    n = len(column)
+    if n >= 1 << 31:
+        raise ValueError("a string column holds 2^31 or more records; a device takes fewer")
+    capacity = _pid_capacity(n, max_distinct)
+    if ctx is not None and dev.type == "cuda":
+        offsets, data = column.device_columns(dev)
+        keys, n_invalid = string_columns.device_keys(offsets, data, column.hash_seed, ctx, sptr)
+        slots = torch.full((capacity,), _I64_MIN, dtype=torch.int64, device=dev)
+        info = torch.zeros(2, dtype=torch.int64, device=dev)
+        rec_slots = torch.empty(n, dtype=torch.int32, device=dev)  # uint32 bit patterns
+        ctx.keydict_insert_slots(keys.data_ptr(), n, slots.data_ptr(), capacity,
+                                 rec_slots.data_ptr(), info.data_ptr(), sptr)
+        del slots
+        rep = torch.full((capacity,), -1, dtype=torch.int32, device=dev)  # 0xFFFFFFFF
+        ctx.keydict_representatives(rec_slots.data_ptr(), n, capacity, rep.data_ptr(), sptr)
+        n_mismatch = torch.zeros(1, dtype=torch.int64, device=dev)
+        ctx.string_verify(offsets.data_ptr(), data.data_ptr(), data.numel(), n,
+                          rec_slots.data_ptr(), rep.data_ptr(), n_mismatch.data_ptr(), sptr)
+        has_rep = rep != -1
+        # the one host synchronisation of the local step
+        D, invalid, _, lost, mismatch = torch.cat(
+            [torch.count_nonzero(has_rep).reshape(1), n_invalid, info, n_mismatch]).tolist()
+        occupied = torch.nonzero_static(has_rep, size=D).view(-1)
+        rep_rec = rep[occupied].to(torch.int64)
+        hashes = keys[rep_rec]
+        del keys, has_rep
+
+        def finish(ids: torch.Tensor) -> torch.Tensor:
+            # the representatives have done their work: their array carries the ids
+            rep[occupied] = ids.to(torch.int32)
+            out = torch.empty(n, dtype=torch.int64, device=dev)
+            n_missing = torch.zeros(1, dtype=torch.int64, device=dev)
+            ctx.keydict_gather_ids(rec_slots.data_ptr(), n, rep.data_ptr(), capacity,
+                                   out.data_ptr(), n_missing.data_ptr(), sptr)
+            return out
+        return offsets, data, hashes, rep_rec, finish, [invalid, lost, mismatch]
+    # host tensors: the same outcome from numpy (first-seen record = representative)
+    h_off, h_data = column.host_columns()
+    keys, invalid = string_columns.host_keys(h_off, h_data, column.hash_seed)
+    uniq, first, inv = np.unique(keys, return_index=True, return_inverse=True)
+    inv = inv.reshape(-1)
+    # the device table's capacity, mirrored: the keys past it find no slot
+    fits = np.ones(uniq.size, dtype=bool)
+    if uniq.size > capacity:
+        fits[np.argsort(first, kind="stable")[capacity:]] = False
+    lost = int((~fits[inv]).sum())
+    start, length, ok = string_columns._np_ranges(h_off, h_data.size, n, np.arange(n))
+    buf = h_data.tobytes()
+    raw = [buf[a:a + ln] if v else None for a, ln, v in zip(start.tolist(), length.tolist(),
+                                                           ok.tolist())]
+    mismatch = sum(1 for i, u in enumerate(inv.tolist())
+                   if fits[u] and (raw[i] is None or raw[i] != raw[first[u]]))
+    new_index = np.cumsum(fits) - 1  # position of a key among the kept ones
+    rep_rec = torch.from_numpy(first[fits].astype(np.int64))
+    hashes = torch.from_numpy(uniq[fits].astype(np.int64))
+
+    def finish(ids: torch.Tensor) -> torch.Tensor:
+        out = np.full(n, -1, dtype=np.int64)
+        kept = fits[inv]
+        out[kept] = ids.numpy()[new_index[inv[kept]]]
+        return torch.from_numpy(out)
+    return (torch.from_numpy(h_off), torch.from_numpy(h_data), hashes, rep_rec, finish,
+            [int(invalid), lost, mismatch])
+
+
+def build_string_dictionary(column, public=None, group=None, ctx=None, device=None,
+                            stream=None, max_distinct: Optional[int] = None) -> StringDictionary:
+    """Global dense ids for a StringColumn of partition keys, the same on every
+    rank, and every rank's slice of the string table
+    (ColumnarData(global_string_keys=True)).
+
+    column: this rank's StringColumn; public: the public partitions as a list
+    of str, the same on every rank, or None.  group: the process group; None =
+    one process (R = 1, no collective).  Device path: `ctx` (the library
+    context) and `device`; without a context the column is taken on the host
+    and numpy restatements of the kernels run the same protocol (the gloo CPU
+    tests), as build_key_dictionary does.
+
+    1. Local, as string_columns.encode_partition_keys: dpg_string_hash (through
+       string_columns.device_keys), dpg_keydict_insert_slots into a table sized
+       by `max_distinct` (else by n), dpg_keydict_representatives,
+       dpg_string_verify, and ONE host synchronisation reading the distinct
+       count D, the invalid-offset, lost and local mismatch counts.  Nothing
+       is raised yet: a rank with errors runs every step below with what it
+       has (a record with invalid offsets or without a slot reads nothing).
+    2. Ids: the D distinct hashes and the hashes of the public strings (the
+       column's hash_seed) go through build_key_dictionary unchanged: owner
+       key_owner(hash, R), global id i * R + owner with i the hash's ascending
+       signed rank among the owner's hashes, P, owned_keys, public_ids.  The
+       ids are scattered to the occupied slots (the representatives' array is
+       reused) and dpg_keydict_gather_ids gives every record its id: 4 B in,
+       8 B out per record, no second probe.
+    3. Strings to owners: the D representative strings, ordered by owner, are
+       packed (dpg_string_lengths, a cumsum over D entries, dpg_string_pack:
+       string_columns.pack_strings) and travel with their hashes and lengths:
+       two `_split_sizes` all_gathers (strings, bytes; a byte or string total
+       of 2^31 or more on any rank raises the same ValueError everywhere) and
+       three all_to_all_single.  The public strings this rank owns are packed
+       from the public column by the same call and join the arrivals as one
+       more source; they are not sent.
+    4. At the owner: the arrivals are sorted by hash with their index as
+       payload (dpg_sort_pairs_u64 on key ^ 2^63; stable, so a run is in
+       source-rank order), dpg_string_verify_runs compares every arrival with
+       its predecessor in the run -- this is where two different strings of
+       two ranks with one hash meet -- and the heads are packed once more, in
+       owned_keys order, into the owned string table (owned_offsets,
+       owned_data; on the device).
+    5. ONE all_reduce (sum) of [invalid offsets, lost, local mismatches, owner
+       mismatches, internal], after which every rank raises the same
+       ValueError, in this order: invalid offsets, table overflow (naming
+       max_distinct_partition_keys), "{k} records or strings share a 64-bit
+       hash with a different string; pass another hash_seed" with k = local +
+       owner mismatches; then RuntimeError when any owner's head count is not
+       len(owned_keys) (internal).
+
+    Collectives with R > 1, run by every rank whatever it holds: the four of
+    build_key_dictionary, two all_gathers, three all_to_all_single and one
+    all_reduce -- ten.  Host synchronisations on the device path: one in step
+    1, three in build_key_dictionary's (its count and split, its lookup
+    check), the split counts and one byte total per packed column (sent,
+    public, owned) and the head count.
+
+    The ids depend only on the union of the string sets, the seed and R.  With
+    R = 1 they are the ascending signed rank of the hashes -- NOT the rank of
+    the sorted strings that string_columns.encode_partition_keys (the default
+    one-process route) gives."""
+    world = 1 if group is None else dist.get_world_size(group)
+    rank = 0 if group is None else dist.get_rank(group)
+    on_device = ctx is not None and device is not None and torch.device(device).type == "cuda"
+    dev = torch.device(device) if on_device else torch.device("cpu")
+    kctx = ctx if on_device else None
+    sptr = stream
+    if on_device and sptr is None:
+        sptr = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    # ---- 1. local
+    offsets, data, hashes, rep_rec, finish, errs = _local_string_keys(
+        column, dev, kctx, sptr, max_distinct)
+    D = int(hashes.numel())
+    # ---- 2. ids
+    pub_col = pub_hash = None
+    if public is not None:
+        pub = string_columns.StringColumn.from_strings(public, column.encoding)
+        if on_device:
+            pub_col = pub.device_columns(dev)
+            pub_hash, _ = string_columns.device_keys(*pub_col, column.hash_seed, ctx, sptr)
+        else:
+            pub_col = tuple(torch.from_numpy(x) for x in pub.host_columns())
+            pub_hash = torch.from_numpy(string_columns.host_keys(
+                *pub.host_columns(), column.hash_seed)[0])
+    kd = build_key_dictionary(hashes, pub_hash, group, kctx, sptr)
+    ids = finish(kd.ids)
+    # ---- 3. strings to owners
+    dest = key_owner(hashes, world)
+    order = torch.argsort(dest, stable=True)
+    s_off, s_data, _ = string_columns.pack_strings(offsets, data, rep_rec[order], kctx, sptr)
+    s_hash = hashes[order]
+    s_len = s_off[1:] - s_off[:-1]
+    if world > 1:
+        counts = torch.bincount(dest, minlength=world).cpu()  # a host synchronisation
+        bounds = torch.cumsum(counts, 0)
+        ends = s_off.cpu()[bounds]
+        nbytes = ends - torch.cat([ends.new_zeros(1), ends[:-1]])
+        in_n, out_n = _split_sizes(counts, group, dev, "string dictionary", "strings")
+        in_b, out_b = _split_sizes(nbytes, group, dev, "string dictionary", "bytes of strings")
+        a_hash = _exchange_column(s_hash, in_n, out_n, group)
+        a_len = _exchange_column(s_len.contiguous(), in_n, out_n, group)
+        a_data = _exchange_column(s_data, in_b, out_b, group)
+    else:
+        a_hash, a_len, a_data = s_hash, s_len, s_data
+    del s_off, s_data, s_hash, s_len
+    if pub_hash is not None:
+        mine = torch.nonzero(key_owner(pub_hash, world) == rank).view(-1)
+        p_off, p_data, _ = string_columns.pack_strings(*pub_col, mine, kctx, sptr)
+        a_hash = torch.cat([a_hash, pub_hash[mine]])
+        a_len = torch.cat([a_len, p_off[1:] - p_off[:-1]])
+        a_data = torch.cat([a_data, p_data])
+    M = int(a_hash.numel())
+    a_off = torch.zeros(M + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(a_len, 0, out=a_off[1:])
+    # a sender's lengths and bytes come from one pack, so the offsets end at
+    # the bytes; anything else is caught by the kernels' range checks
+    # ---- 4. at the owner
+    biased = (a_hash ^ _I64_MIN).contiguous()
+    if on_device:
+        idx = torch.arange(M, dtype=torch.int32, device=dev)
+        srt = torch.empty_like(biased)
+        srt_idx = torch.empty_like(idx)
+        ctx.sort_pairs_u64(biased.data_ptr(), idx.data_ptr(), M, 0, 64, srt.data_ptr(),
+                           srt_idx.data_ptr(), sptr)
+    else:
+        # unsigned order of key ^ 2^63 = signed order of the key
+        o = torch.from_numpy(np.argsort(a_hash.numpy(), kind="stable"))
+        srt, srt_idx = biased[o], o.to(torch.int32)
+    head, owner_info = string_columns.verify_runs(srt, srt_idx, a_off, a_data, kctx, sptr)
+    heads = srt_idx[torch.nonzero(head).view(-1)].to(torch.int64)  # a host synchronisation
+    owned_offsets, owned_data, _ = string_columns.pack_strings(a_off, a_data, heads, kctx, sptr)
+    n_owned = int(kd.owned_keys.numel())
+    internal = int(heads.numel() != n_owned)
+    # ---- 5. every rank's errors, summed
+    t = torch.tensor(errs + [0, internal], dtype=torch.int64)
+    t[3] = owner_info[:1].cpu()[0]
+    if world > 1:
+        t = t.to(_coll_device(group, dev))
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    invalid, lost, mismatch, owner_mismatch, internal = t.tolist()
+    if invalid:
+        raise ValueError(STRING_OFFSETS_ERROR.format(invalid))
+    if lost:
+        raise ValueError(STRING_OVERFLOW_ERROR.format(max_distinct, lost))
+    if mismatch + owner_mismatch:
+        raise ValueError(STRING_COLLISION_ERROR.format(mismatch + owner_mismatch))
+    if internal:
+        raise RuntimeError("string dictionary: an owner's distinct arrivals are not its owned "
+                           "keys (internal error)")
+    return StringDictionary(ids=ids, public_ids=kd.public_ids, n_partitions=kd.n_partitions,
+                            owned_keys=kd.owned_keys, owned_offsets=owned_offsets,
+                            owned_data=owned_data, encoding=column.encoding, ctx=kctx)
 
 
 def place_records(enc, backend, mode: str) -> None:
@@ -1176,13 +1444,44 @@ def slice_bitmap(mask: torch.Tensor, lo: int, stride: int, n: int) -> torch.Tens
     return (padded.view(-1, 8).to(torch.int64) * weights).sum(1).to(torch.uint8)
 
 
-def all_gather_results(ids: torch.Tensor, vals: torch.Tensor, group, exact_ids: bool = False):
+def all_gather_strings(out_offsets: torch.Tensor, out_data: torch.Tensor, sizes, group,
+                       encoding: str = "utf-8") -> list:
+    """Every rank's kept strings (a packed column: offsets int64[K + 1] and
+    bytes) as one list of str in rank order, the same on every rank: ONE
+    all_gather of the lengths, padded to the largest of `sizes` (every rank's
+    K, as all_gather_results exchanged them), and ONE of the bytes, padded to
+    the largest byte total, which the lengths give."""
+    world = dist.get_world_size(group)
+    cdev = _coll_device(group, out_offsets.device)
+    m = max(sizes) if sizes else 0
+    k = out_offsets.numel() - 1
+    mine = torch.zeros(m, dtype=torch.int64, device=cdev)
+    mine[:k] = (out_offsets[1:] - out_offsets[:-1]).to(cdev)
+    lens = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(lens, mine, group=group)
+    lens = [ln[:s].cpu() for ln, s in zip(lens, sizes)]
+    totals = [int(ln.sum().item()) for ln in lens]
+    buf = torch.zeros(max(totals) if totals else 0, dtype=torch.uint8, device=cdev)
+    buf[:out_data.numel()] = out_data.to(cdev)
+    parts = [torch.empty_like(buf) for _ in range(world)]
+    dist.all_gather(parts, buf, group=group)
+    out = []
+    for ln, p, t in zip(lens, parts, totals):
+        off = torch.zeros(ln.numel() + 1, dtype=torch.int64)
+        torch.cumsum(ln, 0, out=off[1:])
+        out += string_columns.decode_packed(off, p[:t], encoding)
+    return out
+
+
+def all_gather_results(ids: torch.Tensor, vals: torch.Tensor, group, exact_ids: bool = False,
+                       return_sizes: bool = False):
     """Concatenates every rank's kept (ids, values) in rank order: one size
     exchange, then one all_gather of ids and values packed as float64 rows
     (ids < 2^53 are exact).  exact_ids: the ids are the caller's sparse int64
     keys, which a float64 does not hold: they travel in an int64 all_gather of
-    their own.  Runs after dpg_compact_kept, which has already synchronised
-    the host."""
+    their own.  return_sizes: every rank's kept count is returned as a third
+    value (a list).  Runs after dpg_compact_kept, which has already
+    synchronised the host."""
     world = dist.get_world_size(group)
     dev = ids.device
     cdev = _coll_device(group, dev)
@@ -1205,5 +1504,7 @@ def all_gather_results(ids: torch.Tensor, vals: torch.Tensor, group, exact_ids: 
         parts = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(parts, mine, group=group)
         keys = torch.cat([p[:s] for p, s in zip(parts, sizes)]).to(dev)
-        return keys, rows[:, 1:].to(vals.dtype).contiguous()
-    return rows[:, 0].round().to(torch.int64), rows[:, 1:].to(vals.dtype).contiguous()
+        out = (keys, rows[:, 1:].to(vals.dtype).contiguous())
+    else:
+        out = (rows[:, 0].round().to(torch.int64), rows[:, 1:].to(vals.dtype).contiguous())
+    return out + (sizes,) if return_sizes else out

@@ -13,6 +13,12 @@ definition is in include/dpg.h and restated here in numpy, `host_keys`).
   per slot, and a byte compare of every record with its slot's representative,
   so a hash collision raises instead of merging two partitions.  Only the D
   distinct strings reach the host, where they are decoded and sorted.
+* With ColumnarData(global_string_keys=True) a partition-key column gets its
+  ids from the hashes instead (`encode_global_partition_keys`,
+  distributed.build_string_dictionary), on one rank or
+  several: the distinct strings are packed on the device (`pack_strings`), sent
+  to their hashes' owners and compared there run by run (`verify_runs`), and
+  only the strings of kept partitions are decoded (`decode_packed`).
 * A privacy-id column is replaced by its keys and takes the wide-id route
   (distributed.encode_privacy_ids).  These hashes are not verified: a
   collision merges two privacy ids into one, which only makes contribution
@@ -199,6 +205,125 @@ def _gather_strings(offsets, data, records: torch.Tensor, encoding: str) -> List
     return [buf[a[i]:a[i] + ln[i]].decode(encoding) for i in range(D)]
 
 
+def _np_ranges(offsets: np.ndarray, data_len: int, n: int, records: np.ndarray):
+    """(start, length, valid) of the given records of an n-record host column,
+    checked as the device checks them; an invalid record has length 0."""
+    records = np.asarray(records, dtype=np.int64)
+    ok = (records >= 0) & (records < n)
+    r = np.where(ok, records, 0)
+    if n == 0:
+        z = np.zeros(records.shape, dtype=np.int64)
+        return z, z.copy(), np.zeros(records.shape, dtype=bool)
+    start, end = offsets[r], offsets[r + 1]
+    ok &= (start >= 0) & (start <= end) & (end <= data_len)
+    return np.where(ok, start, 0), np.where(ok, end - start, 0), ok
+
+
+def host_pack(offsets: np.ndarray, data: np.ndarray, records: np.ndarray):
+    """dpg_string_lengths + prefix sum + dpg_string_pack in numpy: (out_offsets
+    int64[m + 1], out_data uint8, number of invalid records, which get an empty
+    range)."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    start, length, ok = _np_ranges(offsets, data.size, offsets.size - 1, records)
+    out_offsets = np.zeros(length.size + 1, dtype=np.int64)
+    np.cumsum(length, out=out_offsets[1:])
+    total = int(out_offsets[-1])
+    which = np.repeat(np.arange(length.size), length)
+    pos = np.arange(total, dtype=np.int64) - out_offsets[:-1][which] + start[which]
+    return out_offsets, data[pos], int((~ok).sum())
+
+
+def host_verify_runs(keys: np.ndarray, order: Optional[np.ndarray], offsets: np.ndarray,
+                     data: np.ndarray):
+    """dpg_string_verify_runs in numpy: (head uint8[m], differences, of which
+    invalid indices or offsets)."""
+    keys = np.asarray(keys)
+    m = keys.size
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    head = np.ones(m, dtype=np.uint8)
+    if m > 1:
+        head[1:] = keys[1:] != keys[:-1]
+    idx = np.arange(m, dtype=np.int64) if order is None else np.asarray(order).astype(np.int64)
+    start, length, ok = _np_ranges(offsets, data.size, offsets.size - 1, idx)
+    buf = data.tobytes()
+    differ = invalid = 0
+    for j in np.nonzero(head == 0)[0].tolist():
+        if not (ok[j] and ok[j - 1]):
+            differ += 1
+            invalid += 1
+        elif (buf[start[j]:start[j] + length[j]]
+              != buf[start[j - 1]:start[j - 1] + length[j - 1]]):
+            differ += 1
+    return head, differ, invalid
+
+
+def pack_strings(offsets: torch.Tensor, data: torch.Tensor, records: torch.Tensor, ctx=None,
+                 stream=None):
+    """The given records (an int64 index tensor, m entries, any order, repeats
+    allowed) of a column as a packed column of their own: (out_offsets
+    int64[m + 1], out_data uint8, int64[1] count of invalid records), on the
+    column's device.  Device tensors with the library context `ctx`:
+    dpg_string_lengths, a cumsum over m entries, ONE host synchronisation that
+    reads the byte total (the output must be allocated) and dpg_string_pack.
+    Host tensors: the numpy restatement (`host_pack`)."""
+    dev = offsets.device
+    n, m = offsets.numel() - 1, records.numel()
+    if ctx is None or dev.type != "cuda":
+        oo, od, bad = host_pack(offsets.numpy(), data.numpy(), records.numpy())
+        return torch.from_numpy(oo), torch.from_numpy(od), torch.tensor([bad], dtype=torch.int64)
+    records = records.to(torch.int64).contiguous()
+    with torch.cuda.device(dev):
+        if stream is None:
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        out_offsets = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+        info = torch.zeros(2, dtype=torch.int64, device=dev)
+        ctx.string_lengths(offsets.data_ptr(), data.numel(), n, records.data_ptr(), m,
+                           out_offsets.data_ptr() + 8, info.data_ptr(), stream)
+        if m:
+            torch.cumsum(out_offsets[1:], 0, out=out_offsets[1:])
+        total = int(out_offsets[-1].item())  # the one host synchronisation
+        out_data = torch.empty(total, dtype=torch.uint8, device=dev)
+        # an invalid record is counted once, by the lengths: its empty out
+        # range makes the pack count it again, into a slot nobody reads
+        ctx.string_pack(offsets.data_ptr(), data.data_ptr(), data.numel(), n, records.data_ptr(),
+                        m, out_offsets.data_ptr(), out_data.data_ptr(), total,
+                        info.data_ptr() + 8, stream)
+    return out_offsets, out_data, info[:1]
+
+
+def verify_runs(keys: torch.Tensor, order: Optional[torch.Tensor], offsets: torch.Tensor,
+                data: torch.Tensor, ctx=None, stream=None):
+    """dpg_string_verify_runs over a column: (head uint8[m], int64[2] counts of
+    differences and of invalid entries among them) on the keys' device; host
+    tensors take the numpy restatement (`host_verify_runs`).  `order`: int32
+    tensor of uint32 bit patterns, or None."""
+    dev = keys.device
+    m = keys.numel()
+    if ctx is None or dev.type != "cuda":
+        head, differ, invalid = host_verify_runs(
+            keys.numpy(), None if order is None else order.numpy().view(np.uint32),
+            offsets.numpy(), data.numpy())
+        return torch.from_numpy(head), torch.tensor([differ, invalid], dtype=torch.int64)
+    head = torch.empty(m, dtype=torch.uint8, device=dev)
+    info = torch.zeros(2, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        if stream is None:
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ctx.string_verify_runs(keys.data_ptr(), None if order is None else order.data_ptr(),
+                               offsets.data_ptr(), data.data_ptr(), data.numel(),
+                               offsets.numel() - 1, m, head.data_ptr(), info.data_ptr(), stream)
+    return head, info
+
+
+def decode_packed(out_offsets, out_data, encoding: str = "utf-8") -> List[str]:
+    """A packed column (tensors on any device) as a list of str."""
+    off = out_offsets.cpu().tolist()
+    buf = out_data.cpu().numpy().tobytes()
+    return [buf[a:b].decode(encoding) for a, b in zip(off[:-1], off[1:])]
+
+
 def public_strings(public_partitions) -> Optional[List[str]]:
     """Public partitions of a string partition column as a list of str: a
     list or tuple of str, or a StringColumn; else TypeError."""
@@ -284,3 +409,19 @@ def encode_partition_keys(column: StringColumn, public: Optional[List[str]], dev
     public_ids = (None if public is None
                   else np.asarray([index[s] for s in public], dtype=np.int64))
     return ids, table, public_ids
+
+
+def encode_global_partition_keys(column: StringColumn, public: Optional[List[str]], device, ctx,
+                                 max_distinct: Optional[int] = None, group=None):
+    """ColumnarData(global_string_keys=True): the ids of a string partition
+    column from the global string dictionary, on one rank (`group` None) or
+    several -- distributed.build_string_dictionary, which see; returns its
+    StringDictionary (ids of the records and of `public`, P, and this rank's
+    slice of the string table, on the device).  Unlike `encode_partition_keys`
+    the ids are the ascending rank of the HASHES (i * R + owner), no string is
+    decoded or sorted here, and none reaches the host before a partition is
+    kept."""
+    from . import distributed
+    with torch.cuda.device(device):
+        return distributed.build_string_dictionary(column, public, group, ctx, device,
+                                                   max_distinct=max_distinct)
