@@ -117,8 +117,16 @@ static inline double u53(uint32_t a, uint32_t b) {
  * the un-vendored Google DP library used by PyDP: the value
  * is rounded to a power-of-two granularity g ~ scale * 2^-40 and the noise
  * is an integer multiple of g. */
+/* The smallest power of two >= scale * 2^-40, from the exponent of the scale
+ * (granularity() of csrc/dpg_common.h): scale = m * 2^e with m in [0.5, 1),
+ * stepped down when the scale is itself a power of two.  exp2(ceil(log2(.)))
+ * was a factor of two short just above a power of two, where log2 rounds to
+ * the integer. */
 double dpo_granularity(double scale) {
-    return exp2(ceil(log2(scale * 0x1.0p-40)));
+    if (isinf(scale)) return scale;
+    int e;
+    double m = frexp(scale, &e);
+    return ldexp(1.0, (m == 0.5 ? e - 1 : e) - 40);
 }
 
 double dpo_laplace(double x, double b, uint32_t u[4]) {

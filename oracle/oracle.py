@@ -100,6 +100,8 @@ def lib():
         L.dpo_noise_sample.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
         L.dpo_noise_sample.restype = ctypes.c_double
+        L.dpo_granularity.argtypes = [ctypes.c_double]
+        L.dpo_granularity.restype = ctypes.c_double
         L.dpo_philox.argtypes = [ctypes.POINTER(ctypes.c_uint32 * 4),
                                  ctypes.POINTER(ctypes.c_uint32 * 2),
                                  ctypes.POINTER(ctypes.c_uint32 * 4)]
@@ -180,6 +182,10 @@ def rec_prio(seed, pid, pk, gidx):
 
 def noise_sample(kind, x, scale, seed, pk, slot):
     return lib().dpo_noise_sample(kind, x, scale, ctypes.c_uint64(seed), ctypes.c_uint64(pk), slot)
+
+
+def granularity(scale):
+    return lib().dpo_granularity(scale)
 
 
 def philox(ctr, key):

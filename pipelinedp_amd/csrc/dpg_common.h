@@ -310,8 +310,16 @@ __device__ __forceinline__ double u53(uint32_t a, uint32_t b) {
     return ((double)u + 0.5) * 0x1.0p-53;
 }
 
+// The smallest power of two >= scale * 2^-40, from the exponent of the scale
+// alone: scale = m * 2^e with m in [0.5, 1) lies in (2^(e-1), 2^e] once the
+// power of two m == 0.5 is stepped down.  No logarithm: log2 of a scale just
+// above a power of two rounds to the integer, and exp2(ceil(log2(.))) then
+// came out a factor of two too small.
 __device__ __forceinline__ double granularity(double scale) {
-    return exp2(ceil(log2(scale * 0x1.0p-40)));
+    if (isinf(scale)) return scale;
+    int e;
+    const double m = frexp(scale, &e);
+    return ldexp(1.0, (m == 0.5 ? e - 1 : e) - 40);
 }
 
 // The lattice of a noise scale: g = granularity(scale) and its exact
